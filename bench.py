@@ -8,12 +8,17 @@ AnySD (SD-1.5 UNet, in_channels=8, + task embedding / routed expert adapters), b
 A "step" = one full 50-DDIM-step edit of the per-GPU batch; 1 edited image = 150 UNet-sample evaluations = 120.5 TFLOP.
 VAE / CLIP encoders are outside the timed loop and outside this path's scope.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events on the launch stream for the dominant kernel;
-`cpu_baseline` times the oracle (oracle/, our fp32 CPU restatement — test infrastructure, here only as the measured baseline)
-on the host cores for one UNet evaluation (bounded sample) and scales it to the metric's unit.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and reports the headline figure (`value`,
+`ms_per_step`, ...).  --dump-outputs DIR writes the latents the last timed step returned (float32, DIR/latents.npy; one file per
+rank, latents_rank<r>.npy, when there are several) so that two builds can be compared output for output: the weights and the inputs
+are seeded, identical from run to run.  --full adds the legs that take runs of their own: `unet_step_ms_p50` (per-replay HIP-event
+timing of the captured UNet evaluation), `roofline` / `kernels` (measured live with HIP events on the launch stream, dominant kernel
++ per-kernel table, kernels_by_shape.json) and, at one GPU, `cpu_baseline` + `parity`: the oracle (oracle/, our fp32 CPU restatement
+— test infrastructure, here only as the measured baseline) timed on the host cores for one UNet evaluation (bounded sample), scaled
+to the metric's unit, and the full-size HIP-vs-oracle parity of that evaluation.
 """
 import argparse
 import json
@@ -211,11 +216,17 @@ def main():
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--latent", type=int, default=64, help="latent side (64 = the 512x512 metric; 96 = 768x768, configs[4], informational)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--cpu-e2e", action="store_true", help="BASELINE.md §3: also time config 1 (one latent, 20 DDIM steps, k = 3 and k = 2) end to end on the host cores (minutes)")
-    ap.add_argument("--cpu-ops", action="store_true", help="BASELINE.md §3: also time the per-op legs on the host cores")
+    ap.add_argument("--full", action="store_true", help="after the headline figure, also the UNet-step p50, the roofline / per-kernel pass and (1 GPU) the CPU baseline + full-size parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the latents of the last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline / parity leg")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline / per-kernel pass")
+    ap.add_argument("--cpu-e2e", action="store_true", help="BASELINE.md §3: also time config 1 (one latent, 20 DDIM steps, k = 3 and k = 2) end to end on the host cores (minutes; needs --full)")
+    ap.add_argument("--cpu-ops", action="store_true", help="BASELINE.md §3: also time the per-op legs on the host cores (needs --full)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if (args.cpu_e2e or args.cpu_ops) and not args.full:
+        ap.error("--cpu-e2e / --cpu-ops extend the CPU-baseline leg of --full: add --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -268,6 +279,11 @@ def main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert torch.isfinite(out).all(), "non-finite latents"
+    if args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "latents" if world == 1 else f"latents_rank{rank}"
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), out.detach().float().cpu().numpy())
 
     result = None
     if rank == 0:
@@ -294,10 +310,10 @@ def main():
             "unet_tflops_kind": "model FLOPs of the reference graph",
             "unet_tflops_executed": 3 * B * ((GFLOP_PER_UNET_SAMPLE - UP2_SKIPPED_GFLOP[64]) if args.latent == 64 else (2148.3 - UP2_SKIPPED_GFLOP[96]) if args.latent == 96 else float("nan"))
             * n_unet_steps / (ms_per_step * 1e-3) / 1e3,
-            "unet_step_ms_p50_note": "graph replay with the time-embedding chain hoisted out of the step since round 5 (4 launches fewer than rounds <= 4)",
         }
-        # BASELINE.json's second metric: UNet-step ms p50 — per-replay HIP-event timing of the captured UNet evaluation
-        if pipe._graph is not None:
+        # BASELINE.json's second metric: UNet-step ms p50 — per-replay HIP-event timing of the captured UNet evaluation (--full)
+        if args.full and pipe._graph is not None:
+            result["unet_step_ms_p50_note"] = "graph replay with the time-embedding chain hoisted out of the step since round 5 (4 launches fewer than rounds <= 4)"
             evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(41)]
             for e0, e1 in evs:
                 e0.record()
@@ -307,7 +323,7 @@ def main():
             ts = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
             result["unet_step_ms_p50"] = ts[len(ts) // 2]
             result["unet_step_ms_p90"] = ts[int(len(ts) * 0.9)]
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             # eager (un-graphed) UNet evaluation with a HIP-event pair around every kernel launch on the launch stream
             pipe.prepare(img_lat, ehs, null, ref, code)
             pipe._x_in[:, :4].view(3, B, 4, args.latent, args.latent).copy_(x_T.unsqueeze(0))
@@ -352,7 +368,7 @@ def main():
             # calls = module-level calls (a GroupNorm call is 1-3 launches, a split-K conv adds its reduce): launches_per_step counts kernels
             result["kernels"] = {k: {"calls_per_step": v["calls"] // 3, "launches_per_step": v["launches"] // 3, "ms_per_step": v["ms"] / 3, "avg_us": v["avg_us"],
                                      "tflops": v["tflops"], "gbps": v["gbps"]} for k, v in sorted(summ.items(), key=lambda kv: -kv[1]["ms"])}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu, parity = cpu_baseline_and_parity(unet, device, e2e=args.cpu_e2e, per_op=args.cpu_ops)
             result["cpu_baseline"] = cpu
             result["parity"] = parity
