@@ -1,0 +1,285 @@
+"""Route cases and the route ledger of gemm_conv.hip / attention_fast.hip, shared by tests/test_kernel_routes.py and tools/route_check.py.
+
+CASES: one dict per GPU case (op + shape + options); tools/route_check.py builds the seeded operands, runs the op through `ops`, records the
+kernels it launched and checks the output element by element (see that script's docstring for the bound).
+
+LEDGER: one row per kernel instantiation of the two files in the default build, keyed by the template-argument tuple as c++filt prints it
+(`gemm_kernel<192, 320, 1, 2, 4, true, 1, 2, false, 0, 4, 0>`: BM, BN, AMODE (0 dense, 1 conv), WAVES_M, WAVES_N, GLDS, WAVES_K, STAGES,
+CS, LAB, WA, XE; `attn_fast_kernel<D, OCC, SEG2, ABL, BIAS, QG, VSPLIT, SKV, NWV, SKT>`; `attn_pipe_kernel<D, KT, PV16>`).  Each row is
+  ("default", [case ids])   reached with no AE_* variable set, by every case listed;
+  ("knob", "AE_X=v")        reached only under that tuning knob;
+  ("unreachable", "why")    compiled, never launched (the launcher line that excludes it).
+"""
+
+# --------------------------------------------------------------------------------------------------- cases
+# conv: B, H, W, Cin, Cout; stride, ups (0 / 1 nearest / 2 zero-insert), cs (column statistics), k (k_order; None = ops.conv_k_order),
+#       res / addvec / f32 epilogue options
+# up2:  conv3x3_up2 (nearest x2 + conv as four 2x2 convs)
+# gemm: M, N, K; epi ("none" / "geglu" / "gelu"), a2 (Ksplit of the two-source form), cpad (output columns past N: ldc > N), bias, res, f32,
+#       cs (column statistics), rs (row statistics, gemm(rowstats=))
+# ln:   gemm_ln (LayerNorm folded into the GEMM): M, N, K, epi
+# attn: B, H, Nq, Nk, D; lay ("qkv": fused [B*N, 3*H*D] rows for self-attention, q rows + packed kv rows for cross-attention; "bhnd"),
+#       nk2 (second segment), rel (kH, kW: SAM rel-pos bias)
+
+
+def _conv(id, B, H, W, Cin, Cout, **kw):
+    return dict(id=id, op="conv", B=B, H=H, W=W, Cin=Cin, Cout=Cout, **kw)
+
+
+def _gemm(id, M, N, K, **kw):
+    return dict(id=id, op="gemm", M=M, N=N, K=K, **kw)
+
+
+def _attn(id, B, H, Nq, Nk, D, **kw):
+    return dict(id=id, op="attn", B=B, H=H, Nq=Nq, Nk=Nk, D=D, **kw)
+
+
+CASES = [
+    # ---- conv, un-split 192x320 (fill >= 0.85 of whole CU rounds)
+    _conv("c320_slab_b11", 11, 64, 64, 320, 320),                         # M % 192 = 128, slab form (chunk-major K)
+    _conv("c320_slab_cs_b11", 11, 64, 64, 320, 320, cs=True, res=True),   # + column statistics epilogue + residual
+    _conv("c320_slab_b10_w64", 10, 70, 64, 320, 320),                     # M % 192 = 64
+    _conv("c320_slab_m32_w16", 17, 154, 16, 320, 320, cs=True),           # M % 192 = 32, width 16
+    _conv("c320_slab_w48", 21, 48, 48, 320, 320),                         # width 48
+    _conv("c320_slab_w96", 8, 64, 96, 320, 320),                          # width 96 (64x96 latent at batch 8)
+    _conv("c320_slab_w192", 2, 128, 192, 320, 320, addvec=True),          # width 192 = the tile: one image row per tile
+    _conv("c320_wrap_w64h2", 384, 2, 64, 320, 320),                       # short map: 192 / W == H + 1 (a tile runs into the next sample)
+    _conv("c320_wrap_w16h11", 279, 11, 16, 320, 320, cs=True),
+    _conv("c320_wrap_w96h1", 511, 1, 96, 320, 320),
+    _conv("c320_tap_w40", 12, 96, 40, 320, 320),                          # width 40: tiles start mid-row (tap form)
+    _conv("c320_tap_w56_cs", 10, 84, 56, 320, 320, cs=True),              # width 56, tap form + statistics
+    _conv("c320_tap_k0", 11, 64, 64, 320, 320, k=0),                      # tap-major K order on the slab's shape
+    _conv("c320_tap_k0_cs", 11, 64, 64, 320, 320, k=0, cs=True),
+    _conv("c320_s2", 11, 128, 128, 320, 320, stride=2),                   # stride 2 (tap form; 64x64 output maps, M % 192 = 128)
+    _conv("c320_ups", 11, 32, 32, 320, 320, ups=1),                       # nearest x2 gather: the plain loop
+    _conv("c320_ups_cs", 11, 32, 32, 320, 320, ups=1, cs=True),
+    _conv("c320_ups_zero", 11, 32, 32, 320, 320, ups=2),                  # zero-insert x2 (the adjoint of a stride-2 conv)
+    _conv("c128_ups_zero", 3, 16, 24, 640, 1280, ups=2),                 # zero-insert x2 on the 128x128 tile
+    _conv("c64_ups_zero", 2, 5, 7, 64, 128, ups=2),
+    # ---- conv, split-K on the 192x320 tile (product geometries: UNet batch 3 / 6 per edited image)
+    _conv("cs_64x96_b3_l2_640", 3, 32, 48, 640, 640),                     # 512x768: split 5, slab, width 48
+    _conv("cs_64x96_b3_l2_320", 3, 32, 48, 320, 640),                     # split 2, tap form (ragged K range)
+    _conv("cs_64x96_b3_l2_1280", 3, 32, 48, 1280, 640),                   # decoder skip concat
+    _conv("cs_64x96_b3_l2_960", 3, 32, 48, 960, 640),
+    _conv("cs_64x96_b6_l3_1280", 6, 16, 24, 1280, 1280),
+    _conv("cs_64x96_b6_l3_2560", 6, 16, 24, 2560, 1280),
+    _conv("cs_96x64_b3_l2_640", 3, 48, 32, 640, 640),                     # 768x512: width 32
+    _conv("cs_96x64_b6_l3_1280", 6, 24, 16, 1280, 1280),
+    _conv("cs_64x80_b3_l2_640", 3, 32, 40, 640, 640),                     # 512x640: width 40, tap form
+    _conv("cs_64x80_b6_l3_1280", 6, 16, 20, 1280, 1280),                  # split 6: K ranges start mid-tap
+    _conv("cs_64x80_b6_l3_1280_k0", 6, 16, 20, 1280, 1280, k=0),          # tap-major: a tap is 20 K tiles, a range 30
+    _conv("cs_64x80_b6_l3_1920", 6, 16, 20, 1920, 1280),
+    _conv("cs_64x80_b6_l3_640", 6, 16, 20, 640, 1280),
+    _conv("cs_48x64_b3_l2_640", 3, 24, 32, 640, 640),
+    _conv("cs_48x64_b6_l3_1280", 6, 12, 16, 1280, 1280),
+    _conv("cs_48x64_b6_l3_2560", 6, 12, 16, 2560, 1280, cs=True),         # + stand-alone column statistics behind the reduce
+    _conv("cs_f7", 3, 32, 34, 1280, 640),                                 # split 7, width 34, ragged last K range
+    _conv("cs_f8", 6, 16, 16, 1280, 1280),                                # split 8, ragged last K range
+    _conv("cs_f3", 5, 32, 48, 1280, 640),                                 # split 3
+    _conv("cs_f5_ups", 6, 8, 12, 1280, 1280, ups=1),                      # split 5 under the nearest x2 gather: the plain loop
+    _conv("cs_f4_slab", 5, 36, 32, 1280, 640),                            # split 4, slab form
+    _conv("cs_f4_tap", 5, 32, 36, 640, 640),                              # split 4, tap form, width 36
+    _conv("cs_s2_f2", 12, 64, 64, 320, 320, stride=2),                    # stride 2, split 2 (the 64x64 -> 32x32 downsampler at UNet batch 12)
+    _conv("cs_s2_f5", 12, 32, 48, 640, 640, stride=2),                    # stride 2, split 5 (32x48 -> 16x24)
+    # ---- conv, everything else
+    _conv("c128_splitk", 2, 8, 8, 1280, 1280),                            # 128x128 split-K + splitk_reduce_kernel
+    _conv("c128_splitk_cs", 3, 8, 12, 1280, 1280, cs=True),               # + colstats_kernel
+    _conv("c128_splitk_rs", 2, 9, 9, 1224, 1280),                         # register-staged loader (Cin % 64 != 0), split-K
+    _conv("c128_wa", 3, 32, 48, 640, 1280),                               # 128x128 weights-ahead
+    _conv("c128_wa_cs", 3, 40, 41, 640, 1280, cs=True, res=True),         # + statistics epilogue, ragged M
+    _conv("c128_rs", 5, 40, 40, 96, 640, addvec=True),                    # 128x128 register-staged (Cin 96)
+    _conv("c160", 3, 64, 96, 320, 320),                                   # 128x160 (64x96 latent, batch 3)
+    _conv("c160_rs", 3, 64, 95, 96, 320),                                 # 128x160 register-staged
+    _conv("c64x128_tile", 3, 64, 80, 320, 320, f32=True),                 # 128x64 (64x80 latent, batch 3), fp32 output
+    _conv("c64x128_rs", 3, 64, 79, 200, 320),
+    _conv("c64", 2, 10, 13, 64, 100),                                     # 64x64 tile, ragged M and N
+    _conv("c64_rs", 1, 9, 7, 40, 36),
+    _conv("c64_s2", 2, 17, 15, 128, 256, stride=2),
+    dict(id="up2_192", op="up2", B=20, H=24, W=24, Cin=320, Cout=320, cs=False),
+    dict(id="up2_192_cs", op="up2", B=20, H=24, W=24, Cin=320, Cout=320, cs=True),
+    dict(id="up2_128", op="up2", B=3, H=16, W=24, Cin=640, Cout=640, cs=False),
+    dict(id="up2_128_cs", op="up2", B=3, H=16, W=24, Cin=640, Cout=640, cs=True),
+    # ---- dense GEMM
+    _gemm("g320_pp", 24500, 640, 640, bias=True, res=True, cpad=16),      # 192x320 2x4 ping-pong, ragged last tile, ldc > N
+    _gemm("g320_pp_a2", 49000, 320, 1280, a2=640, cpad=8),                # + the two-source form
+    _gemm("g320_geglu", 24500, 1280, 640, epi="geglu", bias=True, cpad=8),  # GEGLU 4x2
+    dict(id="g320_ln_geglu", op="ln", M=24500, N=1280, K=640, epi="geglu"),   # LayerNorm fold XE = 2 on the GEGLU tile
+    dict(id="g320_ln_xetail", op="ln", M=3060, N=3840, K=1280, epi="none"),   # the xe_tail rule (qkv of the 16x16 level)
+    _gemm("g128_ring", 3000, 1280, 1280, bias=True, cpad=8),              # 128x128 three-stage ring (XE 0)
+    _gemm("g128_ring_rs", 3000, 1280, 1280, rs=True),                     # ring, XE 1 (row statistics)
+    dict(id="g128_ring_ln", op="ln", M=3000, N=1280, K=1280, epi="none"),     # ring, XE 2 (LayerNorm fold)
+    _gemm("g192x128_ring", 4000, 1280, 2560, res=True, cpad=8),           # 192x128 three-stage ring
+    _gemm("g64_ring", 700, 256, 1280, cpad=8),                            # 64x64 three-stage ring
+    _gemm("g64_ring_a2", 700, 256, 1344, a2=640),
+    _gemm("g128_wa", 4000, 1024, 640, bias=True, cpad=8),                 # 128x128 weights-ahead
+    _gemm("g128_wa_a2", 4000, 1024, 640, a2=320, epi="gelu"),
+    _gemm("g128_wa_rs", 4000, 1024, 640, rs=True),
+    dict(id="g128_wa_ln", op="ln", M=4000, N=1024, K=640, epi="none"),
+    _gemm("g128_wa_cs", 4000, 1024, 640, cs=True),
+    _gemm("g128_wa_f32", 4000, 1024, 640, f32=True),
+    _gemm("g128_short", 4000, 1024, 128),                                 # kt < 3: the two-stage kernel
+    _gemm("g128_rs", 4000, 1024, 648, cpad=8),                            # K % 64 != 0: register-staged loader
+    _gemm("g128x64", 3800, 576, 512, cpad=8),                             # 128x64 (4x2 waves)
+    _gemm("g128x64_rs", 3800, 576, 520),
+    _gemm("g64", 300, 260, 512, cpad=4),                                  # 64x64
+    _gemm("g64_rs", 300, 260, 520),
+    # ---- attention (fused-qkv rows / packed kv rows; every default row has a case whose last 128-query block is ragged, Nq % 128 != 0 —
+    #      test_ledger_rows_are_well_formed checks it; product shapes with whole blocks are extra cases)
+    _attn("a40_pipe64", 4, 8, 4032, 4032, 40, lay="qkv"),                 # 4032 = 63 x 64 keys: 64-key tiles
+    _attn("a40_pipe128", 4, 8, 3968, 3968, 40, lay="qkv"),                # 3968 = 31 x 128 keys: 128-key tiles
+    _attn("a40_pipe128_nq4000", 4, 8, 4000, 4096, 40, lay="qkv"),         # 128-key tiles, ragged last query block (q rows + kv rows)
+    _attn("a40_pipe_6144", 3, 8, 6144, 6144, 40, lay="qkv"),              # 64x96 latent, B*heads = 24
+    _attn("a40_pipe_5120", 6, 8, 5120, 5120, 40, lay="qkv"),              # 64x80 latent, B*heads = 48
+    _attn("a40_pipe64_b6", 6, 8, 4032, 4032, 40, lay="qkv"),              # 4032 at B*heads = 48: 64-key tiles
+    _attn("a40_4032_b3", 3, 8, 4032, 4032, 40, lay="qkv"),                # 4032 at B*heads = 24: too few 256-query blocks for the pipeline -> VSPLIT
+    _attn("a40_qg2", 8, 8, 4000, 4000, 40, lay="qkv"),                    # Nk % 64 != 0: QG = 2
+    _attn("a40_vsplit", 1, 8, 1000, 1000, 40, lay="qkv"),                 # small grid: VSPLIT
+    _attn("a40_skv", 3, 8, 6144, 77, 40, lay="qkv"),                      # cross-attention, keys resident
+    _attn("a40_skv_ng1", 1, 2, 300, 77, 40, lay="qkv"),                   # 1 / 4 / 8 query groups per block
+    _attn("a40_skv_ng4", 24, 8, 1536, 77, 40, lay="qkv"),
+    _attn("a40_skv_ng8", 18, 8, 4032, 77, 40, lay="qkv"),
+    _attn("a40_skv_seg2", 3, 8, 5120, 77, 40, lay="qkv", nk2=1),          # + the second segment (1 key .. the short form's 64)
+    _attn("a40_skv_seg2max", 6, 8, 4032, 77, 40, lay="qkv", nk2=64),
+    _attn("a40_seg2_long", 1, 8, 1000, 300, 40, lay="qkv", nk2=77),       # second segment, long first segment
+    _attn("a80_vsplit", 3, 8, 1536, 1536, 80, lay="qkv"),                 # 32x48 level self-attention
+    _attn("a80_vsplit_1280", 6, 8, 1280, 1280, 80, lay="qkv"),
+    _attn("a80_vsplit_1500", 3, 8, 1500, 1500, 80, lay="qkv"),            # ragged last query block
+    _attn("a80_skv", 3, 8, 1536, 77, 80, lay="qkv"),
+    _attn("a80_skv_ng8", 48, 8, 1000, 77, 80, lay="qkv"),
+    _attn("a80_skv_seg2", 6, 8, 1280, 77, 80, lay="qkv", nk2=16),
+    _attn("a80_skv_seg2_1000", 6, 8, 1000, 77, 80, lay="qkv", nk2=16),
+    _attn("a80_seg2_long", 2, 8, 1000, 200, 80, lay="qkv", nk2=77),
+    _attn("a80_relwin", 25, 16, 196, 196, 80, lay="bhnd", rel=(14, 14)),  # SAM windows: resident keys
+    _attn("a80_relwin240", 4, 16, 240, 240, 80, lay="bhnd", rel=(15, 16)),  # window > 224 queries: tiled look-up bias
+    _attn("a80_relglobal", 1, 16, 1024, 1024, 80, lay="bhnd", rel=(16, 64)),  # global attention rows of 64 keys
+    _attn("a80_relglobal_1000", 1, 16, 1000, 1024, 80, lay="bhnd", rel=(16, 64)),  # + a ragged last query block
+    _attn("a160", 3, 8, 96, 96, 160, lay="qkv"),                          # 8x12 level (64x96 latent): <= 128 keys, resident
+    _attn("a160_320", 6, 8, 320, 320, 160, lay="qkv"),                    # 16x20 level
+    _attn("a160_48", 3, 8, 48, 48, 160, lay="qkv"),
+    _attn("a160_384", 3, 8, 384, 384, 160, lay="qkv"),                    # 16x24 level: > 128 keys, the tiled kernel
+    _attn("a160_self80", 6, 8, 80, 80, 160, lay="qkv"),                   # 8x10 level self-attention (64x80 latent), B*heads = 48
+    _attn("a160_skv", 6, 8, 80, 77, 160, lay="qkv"),
+    _attn("a160_x96", 3, 8, 96, 77, 160, lay="qkv"),                      # 8x12 / 6x8 level cross-attention
+    _attn("a160_x48", 6, 8, 48, 77, 160, lay="qkv"),
+    _attn("a160_skv_seg2", 3, 8, 384, 77, 160, lay="qkv", nk2=8),
+    _attn("a160_skv_seg2_300", 3, 8, 300, 77, 160, lay="qkv", nk2=8),
+    _attn("a160_seg2_long", 3, 8, 384, 384, 160, lay="qkv", nk2=77),
+    _attn("a160_seg2_long_300", 3, 8, 300, 384, 160, lay="qkv", nk2=77),
+]
+
+CASE_IDS = [c["id"] for c in CASES]
+
+
+# --------------------------------------------------------------------------------------------------- ledger
+def _g(*a):
+    return "gemm_kernel<" + ", ".join(str(x).lower() for x in a) + ">"
+
+
+def _af(*a):
+    return "attn_fast_kernel<" + ", ".join(str(x).lower() for x in a) + ">"
+
+
+_DENSE_ONLY = "instantiated by launch<A_CONV3> through an AMODE-generic statement of a branch that requires !conv at run time (gemm_conv.hip: launch())"
+
+LEDGER = {
+    # dense
+    _g(128, 128, 0, 2, 2, False, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=0"),
+    _g(128, 128, 0, 2, 2, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=0"),
+    _g(128, 128, 0, 2, 2, True, 2, 2, False, 0, 0, 0): ("knob", "AE_GEMM_WK=2"),
+    _g(128, 128, 0, 2, 4, False, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=1"),
+    _g(128, 128, 0, 2, 4, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=1"),
+    _g(128, 128, 0, 4, 2, False, 1, 2, False, 0, 0, 0): ("default", ["g128_rs"]),
+    _g(128, 128, 0, 4, 2, True, 1, 2, False, 0, 0, 0): ("default", ["g128_short"]),
+    _g(128, 128, 0, 4, 2, True, 1, 2, False, 0, 1, 0): ("default", ["g128_wa", "g128_wa_a2", "g128_wa_f32"]),
+    _g(128, 128, 0, 4, 2, True, 1, 2, False, 0, 1, 1): ("default", ["g128_wa_rs"]),
+    _g(128, 128, 0, 4, 2, True, 1, 2, False, 0, 1, 2): ("default", ["g128_wa_ln"]),
+    _g(128, 128, 0, 4, 2, True, 1, 2, True, 0, 0, 0): ("knob", "AE_GEMM_WA=1"),
+    _g(128, 128, 0, 4, 2, True, 1, 2, True, 0, 1, 0): ("default", ["g128_wa_cs"]),
+    _g(128, 128, 0, 4, 2, True, 1, 3, False, 0, 0, 0): ("default", ["g128_ring"]),
+    _g(128, 128, 0, 4, 2, True, 1, 3, False, 0, 0, 1): ("default", ["g128_ring_rs"]),
+    _g(128, 128, 0, 4, 2, True, 1, 3, False, 0, 0, 2): ("default", ["g128_ring_ln"]),
+    _g(128, 160, 0, 2, 2, False, 1, 2, False, 0, 0, 0): ("unreachable", "launch() demotes a 128x160 pick to 128x64 for A_DENSE (gemm_conv.hip: `if (pick == 3 && (... AMODE == A_DENSE ...)) pick = 1`)"),
+    _g(128, 160, 0, 2, 2, True, 1, 2, False, 0, 0, 0): ("unreachable", "launch() demotes a 128x160 pick to 128x64 for A_DENSE (gemm_conv.hip: `if (pick == 3 && (... AMODE == A_DENSE ...)) pick = 1`)"),
+    _g(128, 64, 0, 2, 2, False, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=0"),
+    _g(128, 64, 0, 2, 2, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=0"),
+    _g(128, 64, 0, 4, 2, False, 1, 2, False, 0, 0, 0): ("default", ["g128x64_rs"]),
+    _g(128, 64, 0, 4, 2, True, 1, 2, False, 0, 0, 0): ("default", ["g128x64"]),
+    _g(192, 128, 0, 4, 2, True, 1, 3, False, 0, 0, 0): ("default", ["g192x128_ring"]),
+    _g(192, 320, 0, 2, 4, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_PP=59"),
+    _g(192, 320, 0, 2, 4, True, 1, 2, False, 0, 3, 0): ("default", ["g320_pp", "g320_pp_a2"]),
+    _g(192, 320, 0, 4, 2, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_PP=55"),
+    _g(192, 320, 0, 4, 2, True, 1, 2, False, 0, 3, 0): ("default", ["g320_geglu"]),
+    _g(192, 320, 0, 4, 2, True, 1, 2, False, 0, 3, 2): ("default", ["g320_ln_geglu", "g320_ln_xetail"]),
+    _g(64, 64, 0, 2, 2, False, 1, 2, False, 0, 0, 0): ("default", ["g64_rs"]),
+    _g(64, 64, 0, 2, 2, True, 1, 2, False, 0, 0, 0): ("default", ["g64"]),
+    _g(64, 64, 0, 2, 2, True, 1, 3, False, 0, 0, 0): ("default", ["g64_ring", "g64_ring_a2"]),
+    # conv
+    _g(128, 128, 1, 2, 2, False, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=0"),
+    _g(128, 128, 1, 2, 2, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=0"),
+    _g(128, 128, 1, 2, 2, True, 2, 2, False, 0, 0, 0): ("knob", "AE_GEMM_WK=2"),
+    _g(128, 128, 1, 2, 4, False, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=1"),
+    _g(128, 128, 1, 2, 4, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=1"),
+    _g(128, 128, 1, 4, 2, False, 1, 2, False, 0, 0, 0): ("default", ["c128_rs", "c128_splitk_rs"]),
+    _g(128, 128, 1, 4, 2, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_WA=2"),
+    _g(128, 128, 1, 4, 2, True, 1, 2, False, 0, 1, 0): ("default", ["c128_wa", "c128_splitk", "cs_48x64_b3_l2_640", "cs_48x64_b6_l3_1280", "c128_ups_zero", "up2_128"]),
+    _g(128, 128, 1, 4, 2, True, 1, 2, True, 0, 0, 0): ("knob", "AE_GEMM_WA=2"),
+    _g(128, 128, 1, 4, 2, True, 1, 2, True, 0, 1, 0): ("default", ["c128_wa_cs", "up2_128_cs"]),
+    _g(128, 128, 1, 4, 2, True, 1, 3, False, 0, 0, 0): ("knob", "AE_CONV_DEEP=1"),
+    _g(128, 160, 1, 2, 2, False, 1, 2, False, 0, 0, 0): ("default", ["c160_rs"]),
+    _g(128, 160, 1, 2, 2, True, 1, 2, False, 0, 0, 0): ("default", ["c160"]),
+    _g(128, 64, 1, 2, 2, False, 1, 2, False, 0, 0, 0): ("default", ["c64x128_rs"]),
+    _g(128, 64, 1, 2, 2, True, 1, 2, False, 0, 0, 0): ("default", ["c64x128_tile"]),
+    _g(128, 64, 1, 4, 2, False, 1, 2, False, 0, 0, 0): ("unreachable", "the 8-wave 128x64 tile is dense-only (gemm_conv.hip: `pick == 1 && w8 && !conv`); the AE_LAUNCH macro instantiates it for A_CONV3"),
+    _g(128, 64, 1, 4, 2, True, 1, 2, False, 0, 0, 0): ("unreachable", "the 8-wave 128x64 tile is dense-only (gemm_conv.hip: `pick == 1 && w8 && !conv`); the AE_LAUNCH macro instantiates it for A_CONV3"),
+    _g(192, 128, 1, 4, 2, True, 1, 3, False, 0, 0, 0): ("unreachable", _DENSE_ONLY + ": the 192x128 ring (`!done && deep_pref && !conv && ...`)"),
+    _g(192, 320, 1, 2, 4, True, 1, 2, False, 0, 0, 0): ("default", ["c320_ups", "c320_ups_zero", "cs_f5_ups"]),
+    _g(192, 320, 1, 2, 4, True, 1, 2, False, 0, 3, 0): ("default", ["c320_tap_w40", "c320_tap_k0", "c320_s2", "cs_64x96_b3_l2_320", "cs_64x80_b3_l2_640",
+                                                                      "cs_64x80_b6_l3_1280", "cs_64x80_b6_l3_1280_k0", "cs_64x96_b6_l3_1280",
+                                                                      "cs_64x96_b6_l3_2560", "cs_64x80_b6_l3_1920", "cs_64x80_b6_l3_640",
+                                                                      "cs_f7", "cs_f8", "cs_f3", "cs_f4_tap", "cs_s2_f2", "cs_s2_f5", "up2_192"]),
+    _g(192, 320, 1, 2, 4, True, 1, 2, False, 0, 4, 0): ("default", ["c320_slab_b11", "c320_slab_b10_w64", "c320_slab_w48", "c320_slab_w96", "c320_slab_w192",
+                                                                      "c320_wrap_w64h2", "c320_wrap_w96h1", "cs_64x96_b3_l2_640", "cs_64x96_b3_l2_1280",
+                                                                      "cs_64x96_b3_l2_960", "cs_96x64_b3_l2_640", "cs_96x64_b6_l3_1280", "cs_f4_slab"]),
+    _g(192, 320, 1, 2, 4, True, 1, 2, True, 0, 0, 0): ("default", ["c320_ups_cs"]),
+    _g(192, 320, 1, 2, 4, True, 1, 2, True, 0, 3, 0): ("default", ["c320_tap_w56_cs", "c320_tap_k0_cs", "up2_192_cs"]),
+    _g(192, 320, 1, 2, 4, True, 1, 2, True, 0, 4, 0): ("default", ["c320_slab_cs_b11", "c320_slab_m32_w16", "c320_wrap_w16h11"]),
+    _g(192, 320, 1, 4, 2, True, 1, 2, False, 0, 0, 0): ("unreachable", "the 4x2-wave 192x320 plain loop serves GEGLU only (gemm_conv.hip: `else if (a.epi == EPI_GEGLU)`); a conv's epilogue is never GEGLU"),
+    _g(64, 64, 1, 2, 2, False, 1, 2, False, 0, 0, 0): ("default", ["c64_rs"]),
+    _g(64, 64, 1, 2, 2, True, 1, 2, False, 0, 0, 0): ("default", ["c64", "c64_s2", "c64_ups_zero"]),
+    _g(64, 64, 1, 2, 2, True, 1, 3, False, 0, 0, 0): ("unreachable", _DENSE_ONLY + ": the 64x64 ring (`deep_pref && glds && !conv && ...`)"),
+    "splitk_reduce_kernel": ("default", ["c128_splitk", "cs_64x96_b3_l2_640", "cs_64x80_b6_l3_1280", "cs_64x96_b6_l3_2560", "cs_64x80_b6_l3_1920",
+                                         "cs_64x80_b6_l3_640", "cs_48x64_b6_l3_1280", "cs_f7", "cs_f8", "cs_f3", "cs_f4_slab", "cs_f4_tap",
+                                         "cs_f5_ups", "cs_s2_f2", "cs_s2_f5"]),
+    "colstats_kernel": ("default", ["c128_splitk_cs", "cs_48x64_b6_l3_2560"]),
+    # attention
+    _af(160, 1, False, 0, 0, 1, False, True, 4, 3): ("default", ["a160_skv", "a160", "a160_48", "a160_self80", "a160_x96", "a160_x48"]),
+    _af(160, 1, True, 0, 0, 1, False, False, 4, 3): ("default", ["a160_seg2_long", "a160_seg2_long_300"]),
+    _af(160, 1, True, 0, 0, 1, False, True, 4, 3): ("default", ["a160_skv_seg2", "a160_skv_seg2_300"]),
+    _af(160, 2, False, 0, 0, 1, False, False, 4, 3): ("default", ["a160_320", "a160_384"]),
+    _af(160, 2, False, 0, 1, 1, False, False, 4, 3): ("unreachable", "ae_attn_fast_launch refuses D = 160 with a rel-pos bias (attention_fast.hip: `return (a.rel_h || !f160) ? AE_ERR_UNSUPPORTED`)"),
+    _af(160, 2, False, 0, 2, 1, False, False, 4, 3): ("unreachable", "ae_attn_fast_launch refuses D = 160 with a rel-pos bias (attention_fast.hip: `return (a.rel_h || !f160) ? AE_ERR_UNSUPPORTED`)"),
+    _af(160, 3, False, 0, 0, 1, False, False, 4, 3): ("unreachable", "launch_fast<160> returns at `if constexpr (D > 96)` before the OCC-3 statements that instantiate it"),
+    _af(160, 3, False, 0, 0, 1, True, False, 4, 3): ("unreachable", "launch_fast<160> returns at `if constexpr (D > 96)` before the OCC-3 statements that instantiate it"),
+    _af(40, 3, False, 0, 0, 1, False, False, 4, 3): ("knob", "AE_ATTN_V=0"),
+    _af(40, 3, False, 0, 0, 1, False, True, 4, 3): ("default", ["a40_skv", "a40_skv_ng1", "a40_skv_ng4", "a40_skv_ng8"]),
+    _af(40, 3, False, 0, 0, 1, True, False, 4, 3): ("default", ["a40_vsplit", "a40_4032_b3"]),
+    _af(40, 3, False, 0, 0, 2, True, False, 4, 3): ("default", ["a40_qg2"]),
+    _af(40, 3, True, 0, 0, 1, False, False, 4, 3): ("default", ["a40_seg2_long"]),
+    _af(40, 3, True, 0, 0, 1, False, True, 4, 3): ("default", ["a40_skv_seg2", "a40_skv_seg2max"]),
+    _af(80, 2, False, 0, 0, 1, False, True, 4, 3): ("default", ["a80_skv", "a80_skv_ng8"]),
+    _af(80, 2, False, 0, 1, 1, False, False, 4, 3): ("default", ["a80_relwin240"]),
+    _af(80, 2, False, 0, 2, 1, False, False, 4, 3): ("default", ["a80_relglobal", "a80_relglobal_1000"]),
+    _af(80, 2, False, 0, 3, 1, False, True, 7, 4): ("default", ["a80_relwin"]),
+    _af(80, 2, True, 0, 0, 1, False, False, 4, 3): ("default", ["a80_seg2_long"]),
+    _af(80, 2, True, 0, 0, 1, False, True, 4, 3): ("default", ["a80_skv_seg2", "a80_skv_seg2_1000"]),
+    _af(80, 3, False, 0, 0, 1, False, False, 4, 3): ("knob", "AE_ATTN_V=0"),
+    _af(80, 3, False, 0, 0, 1, True, False, 4, 3): ("default", ["a80_vsplit", "a80_vsplit_1280", "a80_vsplit_1500"]),
+    "attn_pipe_kernel<40, 128, false>": ("default", ["a40_pipe128", "a40_pipe128_nq4000", "a40_pipe_6144", "a40_pipe_5120"]),
+    "attn_pipe_kernel<40, 128, true>": ("knob", "AE_ATTN_PV16=1"),
+    "attn_pipe_kernel<40, 64, false>": ("default", ["a40_pipe64", "a40_pipe64_b6"]),
+}
+
+
+def expected_kernels(case_id):
+    """ledger keys whose `default` row lists this case"""
+    return sorted(k for k, (kind, v) in LEDGER.items() if kind == "default" and case_id in v)

@@ -1,0 +1,103 @@
+"""Route ledger of gemm_conv.hip / attention_fast.hip (tests/route_cases.py) and the GPU route cases behind it.
+
+CPU: the set of kernel instantiations the default build compiles — hipcc's device-only LLVM IR of the two sources with the library's flags
+(at -O0: which kernels a translation unit emits does not depend on the optimisation level) — must equal the ledger's keys, in both
+directions, so an instantiation that is added or removed fails here until someone classifies it.
+
+GPU: tools/route_check.py in a fresh child process with every AE_* variable removed from its environment (this test session itself runs
+with AE_ROWPANEL_ANY_M=1, set by test_hip_ops.py): every case must reach its declared instantiations, pass the element-wise float64
+check, leave its guard areas untouched and repeat bit for bit; every `default` ledger row must be reached by each case it lists.
+"""
+import json
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import route_cases as RC  # noqa: E402
+
+FAMILY_RE = re.compile(r"^void (?:\(anonymous namespace\)::)?(gemm_kernel|attn_fast_kernel|attn_pipe_kernel)<([^<>]*)>\(")
+PLAIN = ("splitk_reduce_kernel", "colstats_kernel")
+
+
+def _kernel_keys(ir_text):
+    mangled = re.findall(r"^define\b[^@\n]*\bamdgpu_kernel\b[^@\n]*@(\S+?)\(", ir_text, re.M)
+    dm = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout.split("\n")
+    keys = []
+    for name in dm[:len(mangled)]:
+        m = FAMILY_RE.match(name)
+        if m:
+            keys.append(f"{m.group(1)}<{', '.join(x.strip() for x in m.group(2).split(','))}>")
+        else:
+            keys += [p for p in PLAIN if re.search(r"::" + p + r"\(|^" + p + r"\(", name)]
+    return keys
+
+
+def compiled_instantiations(tmpdir):
+    from anyedit_amd import build as B
+    hipcc = B._hipcc()
+    keys = []
+    for src in ("gemm_conv.hip", "attention_fast.hip"):
+        flags = [("-O0" if f == "-O3" else f) for f in B.FLAGS if f != "-fPIC"] + B.EXTRA.get(src, [])
+        out = os.path.join(str(tmpdir), src.replace(".hip", ".ll"))
+        subprocess.run([hipcc] + flags + ["--cuda-device-only", "-emit-llvm", "-S", os.path.join(B.CSRC, src), "-o", out], check=True,
+                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        with open(out) as f:
+            keys += _kernel_keys(f.read())
+    return keys
+
+
+def test_ledger_rows_are_well_formed():
+    ids = set(RC.CASE_IDS)
+    assert len(ids) == len(RC.CASES), "duplicate case ids"
+    for key, row in RC.LEDGER.items():
+        kind, what = row
+        assert kind in ("default", "knob", "unreachable"), (key, kind)
+        if kind == "default":
+            assert what and all(c in ids for c in what), (key, [c for c in what if c not in ids])
+        elif kind == "knob":
+            assert re.fullmatch(r"AE_[A-Z0-9_]+=\S+", what), (key, what)
+        else:
+            assert len(what) > 20, (key, "an unreachable row says why")
+    for c in RC.CASES:
+        assert c["op"] in ("conv", "up2", "gemm", "ln", "attn"), c
+    # every case asserts a route: it appears in at least one `default` row
+    listed = {c for kind, what in RC.LEDGER.values() if kind == "default" for c in what}
+    assert not ids - listed, f"cases that assert no route: {sorted(ids - listed)}"
+    # every attention row is reached by at least one case whose last 128-query block is ragged
+    nq = {c["id"]: c["Nq"] for c in RC.CASES if c["op"] == "attn"}
+    whole = [k for k, (kind, what) in RC.LEDGER.items() if kind == "default" and k.startswith("attn_") and all(nq[c] % 128 == 0 for c in what)]
+    assert not whole, f"attention rows reached only at Nq % 128 == 0: {whole}"
+
+
+def test_ledger_equals_the_compiled_instantiations(tmp_path):
+    keys = compiled_instantiations(tmp_path)
+    assert len(keys) == len(set(keys)), "a kernel key appears twice"
+    assert sum(k.startswith("gemm_kernel<") for k in keys) > 40 and sum(k.startswith("attn_") for k in keys) > 20, keys
+    compiled, ledger = set(keys), set(RC.LEDGER)
+    assert not compiled - ledger, f"instantiations without a ledger row (classify them in tests/route_cases.py): {sorted(compiled - ledger)}"
+    assert not ledger - compiled, f"ledger rows for instantiations the default build no longer compiles: {sorted(ledger - compiled)}"
+
+
+@pytest.mark.gpu
+def test_route_cases_on_gpu():
+    env = {k: v for k, v in os.environ.items() if not k.startswith("AE_")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "route_check.py")], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=1200)
+    print(p.stdout)
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("ROUTE_SUMMARY ")]
+    assert lines, f"route_check.py ended without a summary (exit {p.returncode}):\n{p.stdout[-4000:]}\n{p.stderr[-4000:]}"
+    summary = json.loads(lines[-1][len("ROUTE_SUMMARY "):])
+    assert summary["aborted"] is None, f"GPU work stopped at {summary['aborted']}"
+    results = {r["id"]: r for r in summary["results"]}
+    assert set(results) == set(RC.CASE_IDS), sorted(set(RC.CASE_IDS) - set(results))
+    failed = {i: r["error"] for i, r in results.items() if not r["ok"]}
+    assert not failed, failed
+    unreached = [(k, c) for k, (kind, cases) in RC.LEDGER.items() if kind == "default" for c in cases if k not in results[c]["keys"]]
+    assert not unreached, unreached
+    assert p.returncode == 0, p.stderr[-4000:]
