@@ -120,6 +120,10 @@ SIGNATURES = {
     "ae_lincomb4_f32": [c_void_p, c_void_p, c_float, c_void_p, c_float, c_void_p, c_float, c_void_p, c_float, c_long, c_void_p],
     "ae_dpm_adaptive_err_f32": [c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_long, c_void_p, c_void_p],
     "ae_task_gate": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ae_attn_causal_short_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_long] * 12 + [c_float, c_void_p],
+    "ae_clip_embed_bf16": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "ae_bias_act_f32_bf16": [c_void_p, c_long, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_void_p],
+    "ae_clip_pool_eos_bf16": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p],
 }
 _RESTYPES = {"ae_last_error": ctypes.c_char_p, "ae_groupnorm_workspace_floats": c_long, "ae_conv3x3_workspace_floats": c_long,
              "ae_groupnorm_bwd_workspace_floats": c_long, "ae_attn_fp8_workspace_bytes": c_long, "ae_attn_bwd_workspace_floats": c_long,

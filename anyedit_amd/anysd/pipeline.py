@@ -14,10 +14,13 @@ from anyedit_amd.ldm.models.diffusion.ddim import DDIMSampler, _f32
 
 
 class EditPipeline:
-    def __init__(self, moe, schedule_model, use_graph=True):
+    def __init__(self, moe, schedule_model, use_graph=True, text_encoder=None):
         """moe: anysd.MoE (or any object with prepare_conditioning/denoise); schedule_model: the DDPM-duck-typed owner of
-        betas/alphas_cumprod (anyedit_amd.ldm.models.diffusion.ddpm.DDPM or a reference LatentDiffusion)."""
+        betas/alphas_cumprod (anyedit_amd.ldm.models.diffusion.ddpm.DDPM or a reference LatentDiffusion); text_encoder: an optional
+        `FrozenCLIPEmbedder` for `edit_text` (instructions instead of encoder hidden states)."""
         self.moe = moe
+        self.text_encoder = text_encoder
+        self._null_ehs, self._null_tok = None, None
         self.sampler = DDIMSampler(schedule_model)
         self.schedule_model = schedule_model
         self.use_graph = use_graph
@@ -118,6 +121,38 @@ class EditPipeline:
             if any(x.shape != y.shape or x.dtype != y.dtype for x, y in zip(a, b)):
                 return False
         return True
+
+    # ------------------------------------------------------------------------------------------------------------
+    def _prompt_ids(self, prompts_or_ids):
+        """Instructions (str / list of str: tokenized as modules.py:136-138 does) or ready [B, N] token ids -> ids."""
+        te = self.text_encoder
+        if isinstance(prompts_or_ids, str) or (isinstance(prompts_or_ids, (list, tuple)) and prompts_or_ids and isinstance(prompts_or_ids[0], str)):
+            tok = te._need_tokenizer()
+            return tok(prompts_or_ids, truncation=True, max_length=te.max_length, return_length=True, return_overflowing_tokens=False,
+                       padding="max_length", return_tensors="pt")["input_ids"]
+        return prompts_or_ids
+
+    def null_prompt_ehs(self):
+        """The empty prompt's hidden states [1, N, C] ([BOS, EOS, PAD x 75], global_tool.py:360-396's negative prompt): encoded once, served from
+        a cache until the encoder's weights change."""
+        te = self.text_encoder
+        tok = te.transformer.weights_token()
+        if self._null_ehs is None or self._null_tok != tok:
+            cfg = te.transformer.config
+            n = min(te.max_length, cfg["max_position_embeddings"])
+            ids = [[cfg["bos_token_id"], cfg["eos_token_id"]] + [cfg["pad_token_id"]] * (n - 2)]
+            self._null_ehs, self._null_tok = te.encode_ids(ids).clone(), tok
+        return self._null_ehs
+
+    @torch.no_grad()
+    def edit_text(self, x_T, img_lat, prompts_or_ids, ref_embeds, edit_code, **edit_kwargs):
+        """`edit` from the instruction itself: prompts (needs the encoder's tokenizer) or [B, N] token ids are encoded by the HIP text tower,
+        the empty prompt comes from the cache, and the rest is `edit(x_T, img_lat, ehs, null_ehs, ref_embeds, edit_code, **edit_kwargs)`."""
+        if self.text_encoder is None:
+            raise ValueError("edit_text: this pipeline was built without a text_encoder (EditPipeline(..., text_encoder=FrozenCLIPEmbedder(...)))")
+        null_ehs = self.null_prompt_ehs()
+        ehs = self.text_encoder.encode_ids(self._prompt_ids(prompts_or_ids))
+        return self.edit(x_T, img_lat, ehs, null_ehs, ref_embeds, edit_code, **edit_kwargs)
 
     @torch.no_grad()
     def edit(self, x_T, img_lat, ehs, null_ehs, ref_embeds, edit_code, steps=50, s_txt=7.5, s_img=1.5, eta=0.0, mask=None,

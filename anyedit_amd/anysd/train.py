@@ -24,8 +24,9 @@ BF16 = torch.bfloat16
 
 class AnySDTrainer:
     def __init__(self, moe, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=1e-2, process_group=None, bucket_bytes=25 << 20, always_exchange=False, force_collectives=False):
+                 weight_decay=1e-2, process_group=None, bucket_bytes=25 << 20, always_exchange=False, force_collectives=False, text_encoder=None):
         self.moe = moe
+        self.text_encoder = text_encoder   # optional FrozenCLIPEmbedder: a batch may then carry input_ids instead of hidden states (train.py:644)
         self.sqrt_ac = sqrt_alphas_cumprod.float()
         self.sqrt_1mac = sqrt_one_minus_alphas_cumprod.float()
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
@@ -55,12 +56,17 @@ class AnySDTrainer:
     # ------------------------------------------------------------------------------------------------ forward on the tape
     def forward_loss(self, latents, image_cond, encoder_hidden_states, ref_embeds, edit_code, noise, timesteps, null_ehs=None,
                      dropout_u=None, dropout_p=0.05):
-        """Returns (loss scalar tensor, tape, leaves) with the forward recorded; call `backward` next."""
+        """Returns (loss scalar tensor, tape, leaves) with the forward recorded; call `backward` next.  `encoder_hidden_states`: [B, L, Dc] hidden
+        states, or — with a `text_encoder` — the [B, N] token ids they are encoded from."""
         moe, dev = self.moe, latents.device
         B = latents.shape[0]
         sa, s1 = self.sqrt_ac.to(dev)[timesteps], self.sqrt_1mac.to(dev)[timesteps]
         noisy = ops.q_sample(latents.float(), noise.float(), sa, s1)
         ehs = encoder_hidden_states
+        if not torch.is_floating_point(torch.as_tensor(ehs)):   # [B, N] token ids: train.py:644 text_encoder(input_ids)[0] — frozen, outside the tape
+            if self.text_encoder is None:
+                raise ValueError("forward_loss: the batch carries token ids but the trainer has no text_encoder (AnySDTrainer(..., text_encoder=))")
+            ehs = self.text_encoder.transformer(ehs)[0].clone()
         if dropout_u is not None:  # train.py:652-669: one draw u per sample decides prompt / image dropout
             prompt_mask, image_mask = conditioning_dropout_masks(dropout_u, dropout_p)
             if null_ehs is not None:

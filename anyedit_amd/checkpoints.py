@@ -187,3 +187,47 @@ def load_unet_weights(unet, path, location="cpu"):
         return "ldm-checkpoint"
     unet.load_state_dict(convert_diffusers_unet(unet, sd))
     return "diffusers"
+
+
+def text_encoder_state_dict(embedder, sd):
+    """The CLIP text tower's entries of a state dict, in `embedder`'s (FrozenCLIPEmbedder) key layout.  Recognised forms: a full SD-1.5
+    checkpoint (`cond_stage_model.transformer.text_model.*`), the tower alone (`transformer.text_model.*`), a transformers CLIPTextModel
+    (`text_model.*`) and newer transformers that dropped that level (`embeddings.*`, `encoder.*`, `final_layer_norm.*`).  The
+    `position_ids` buffer of old checkpoints is dropped.  Every parameter of the tower must be found with its shape; anything else raises."""
+    own = embedder.state_dict()
+    hit = None
+    for pref in ("cond_stage_model.", "", "text_encoder."):
+        for strip in ("", "transformer.", "transformer.text_model."):     # the file's keys lack this leading part of ours
+            if all(pref + k[len(strip):] in sd for k in own):
+                hit = {k: sd[pref + k[len(strip):]] for k in own}
+                break
+        if hit is not None:
+            break
+    if hit is None:
+        raise KeyError(f"no CLIP text tower found: none of the known layouts holds all {len(own)} tensors (e.g. '{next(iter(own))}')")
+    for k, v in hit.items():
+        if tuple(v.shape) != tuple(own[k].shape):
+            raise ValueError(f"{k}: shape {tuple(v.shape)} in the file, {tuple(own[k].shape)} in the tower")
+    return hit
+
+
+def load_sd_checkpoint(path, unet=None, vae=None, text_encoder=None, location="cpu"):
+    """`load_unet_weights`' sibling for a FULL SD-1.5 state dict (CompVis lineage): routes `model.diffusion_model.*` to `unet`,
+    `first_stage_model.*` to `vae` and `cond_stage_model.*` to `text_encoder` (a FrozenCLIPEmbedder); a part given as None is skipped.
+    Returns the names of the parts that were filled."""
+    from anyedit_amd.cldm.model import load_state_dict
+    sd = load_state_dict(path, location)
+    done = []
+    for name, mod, pref in (("unet", unet, "model.diffusion_model."), ("vae", vae, "first_stage_model.")):
+        if mod is None:
+            continue
+        own = [k for k in mod.state_dict().keys() if not k.startswith("loss.")]
+        missing = [k for k in own if pref + k not in sd]
+        if missing:
+            raise KeyError(f"{name}: {len(missing)} tensors are not in the checkpoint under '{pref}' (e.g. '{missing[0]}')")
+        mod.load_state_dict({k: sd[pref + k] for k in own}, strict=False)
+        done.append(name)
+    if text_encoder is not None:
+        text_encoder.load_state_dict(text_encoder_state_dict(text_encoder, sd))
+        done.append("text_encoder")
+    return done

@@ -135,15 +135,48 @@ class LatentDiffusion(DDPM):
                                                                          if k not in ("force_null_conditioning", "use_ema")})
         self.scale_factor = scale_factor
         self.first_stage_model = None
-        self.cond_stage_model = None   # CLIP text tower: outside the hot path (the caller passes its hidden states)
+        self.cond_stage_model = None
+        self.cond_stage_forward = kwargs.get("cond_stage_forward", None)
         if first_stage_config is not None:
             self.instantiate_first_stage(first_stage_config)
+        if cond_stage_config is not None:
+            self.instantiate_cond_stage(cond_stage_config)
 
     def instantiate_first_stage(self, config):
         """ddpm.py:615-620.  `config` is an {'target', 'params'} dict resolved inside this package (ldm.* -> anyedit_amd.ldm.*)
         or an already built first-stage module."""
         vae = config if isinstance(config, nn.Module) else instantiate_from_config(config)
         self.first_stage_model = vae.eval().requires_grad_(False)
+
+    def instantiate_cond_stage(self, config):
+        """ddpm.py:622-640, frozen branch.  A config whose target resolves to this package's FrozenCLIPEmbedder (the CLIP text tower on HIP) or
+        an already built one is installed frozen; the two placeholder strings and every other target leave `cond_stage_model = None` (the
+        caller then passes encoder hidden states, as before)."""
+        from anyedit_amd.ldm.modules.encoders.modules import FrozenCLIPEmbedder
+        from anyedit_amd.ldm.util import get_obj_from_str
+        model = None
+        if isinstance(config, FrozenCLIPEmbedder):
+            model = config
+        elif isinstance(config, dict) and "target" in config:
+            try:
+                cls = get_obj_from_str(config["target"])
+            except (ImportError, AttributeError):
+                cls = None
+            if cls is FrozenCLIPEmbedder:
+                model = cls(**config.get("params", {}))
+        self.cond_stage_model = None if model is None else model.eval().requires_grad_(False)
+
+    def get_learned_conditioning(self, c):
+        """ddpm.py:664-677."""
+        if self.cond_stage_model is None:
+            raise RuntimeError("get_learned_conditioning: this LatentDiffusion has no cond stage (cond_stage_config was None, a placeholder or a "
+                               "target other than FrozenCLIPEmbedder): pass the encoder hidden states yourself")
+        if self.cond_stage_forward is None:
+            if hasattr(self.cond_stage_model, 'encode') and callable(self.cond_stage_model.encode):
+                return self.cond_stage_model.encode(c)
+            return self.cond_stage_model(c)
+        assert hasattr(self.cond_stage_model, self.cond_stage_forward)
+        return getattr(self.cond_stage_model, self.cond_stage_forward)(c)
 
     def get_first_stage_encoding(self, encoder_posterior):
         """ddpm.py:655-662."""

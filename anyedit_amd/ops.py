@@ -828,6 +828,87 @@ def attention_bhnd(q, k, v, scale=None, key_mask=None):
     return out
 
 
+# --------------------------------------------------------------------------- CLIP text tower (csrc/clip_text.hip)
+ACT_QUICK_GELU, ACT_GELU = 0, 1
+
+
+def attention_causal_short(q, k, v, B, H, N, D, scale, q_strides, k_strides, v_strides, out=None):
+    """Causal self-attention over at most 128 tokens (the CLIP text tower): q/k/v bf16 tensors addressed through (batch, head, row)
+    element strides as in `attention`, out [B, N, H*D] bf16.  Row i attends keys [0, i].  N in [1, 128], D in {32, 64}."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _chk(t, BF16, "attention_causal_short." + n)
+    if out is None:
+        out = torch.empty(B, N, H * D, dtype=BF16, device=q.device)
+    _chk(out, BF16, "attention_causal_short.out")
+    if out.numel() != B * N * H * D or not out.is_contiguous():
+        raise ValueError(f"attention_causal_short: out must be a contiguous [{B}, {N}, {H * D}] buffer")
+    check(lib.ae_attn_causal_short_bf16(_p(q), _p(k), _p(v), _p(out), B, H, N, D, *q_strides, *k_strides, *v_strides, N * H * D, D, H * D,
+                                        float(scale), _s()), "ae_attn_causal_short_bf16")
+    return out
+
+
+def clip_embed(ids, token_table, position_table, out=None):
+    """token_table[ids] + position_table[0:N] -> bf16 rows [B*N, C].  ids: int32 / int64 GPU tensor [B, N]; the tables are bf16 [vocab, C]
+    and [positions, C].  The ids are NOT read back to the host (that would be a synchronisation): an id outside [0, vocab) is clamped
+    into the table by the kernel.  Range-check ids while they are still on the host (`FrozenCLIPEmbedder.encode_ids` does)."""
+    if not ids.is_cuda:
+        raise ValueError("clip_embed.ids: expected a GPU tensor (anyedit_amd has no CPU path)")
+    if ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 2 or not ids.is_contiguous():
+        raise TypeError(f"clip_embed.ids: expected a contiguous int32 / int64 [B, N] tensor, got {ids.dtype} {tuple(ids.shape)}")
+    _chk(token_table, BF16, "clip_embed.token_table", 2)
+    _chk(position_table, BF16, "clip_embed.position_table", 2)
+    B, N = ids.shape
+    V, C = token_table.shape
+    if position_table.shape[1] != C or not token_table.is_contiguous() or not position_table.is_contiguous():
+        raise ValueError("clip_embed: the two tables must be contiguous and of one width")
+    if out is None:
+        out = torch.empty(B * N, C, dtype=BF16, device=ids.device)
+    _chk(out, BF16, "clip_embed.out", 2)
+    if tuple(out.shape) != (B * N, C) or not out.is_contiguous():
+        raise ValueError(f"clip_embed: out must be a contiguous [{B * N}, {C}] buffer")
+    check(lib.ae_clip_embed_bf16(_p(ids), 1 if ids.dtype == torch.int64 else 0, _p(token_table), _p(position_table), _p(out), B, N, C, V,
+                                 position_table.shape[0], _s()), "ae_clip_embed_bf16")
+    return out
+
+
+def bias_act(u, bias, act=ACT_QUICK_GELU, out=None):
+    """y = act(u + bias) as bf16, u the fp32 [M, N] product of `gemm(..., out_f32=True)`: the pre-activation is never rounded.
+    act: ACT_QUICK_GELU (t * sigmoid(1.702 t)) or ACT_GELU (erf)."""
+    _chk(u, torch.float32, "bias_act.u", 2)
+    _chk(bias, torch.float32, "bias_act.bias", 1)
+    M, N = u.shape
+    if u.stride(1) != 1 or bias.numel() != N:
+        raise ValueError("bias_act: u needs unit inner stride and bias one value per column")
+    if out is None:
+        out = torch.empty(M, N, dtype=BF16, device=u.device)
+    _chk(out, BF16, "bias_act.out", 2)
+    if tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise ValueError(f"bias_act: out must be [{M}, {N}] with unit inner stride")
+    check(lib.ae_bias_act_f32_bf16(_p(u), u.stride(0), _p(bias), _p(out), out.stride(0), M, N, int(act), _s()), "ae_bias_act_f32_bf16")
+    return out
+
+
+def clip_pool_eos(ids, z, eos_token_id, out=None):
+    """pooler_output of the CLIP text tower: z[b, first position of eos_token_id in ids[b]] -> [B, C] bf16 (position 0 when a prompt has no
+    eos).  ids int32 / int64 [B, N] on the GPU, z bf16 [B*N, C] contiguous.  The position is found on the device."""
+    if not ids.is_cuda:
+        raise ValueError("clip_pool_eos.ids: expected a GPU tensor (anyedit_amd has no CPU path)")
+    if ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 2 or not ids.is_contiguous():
+        raise TypeError(f"clip_pool_eos.ids: expected a contiguous int32 / int64 [B, N] tensor, got {ids.dtype} {tuple(ids.shape)}")
+    _chk(z, BF16, "clip_pool_eos.z", 2)
+    B, N = ids.shape
+    C = z.shape[1]
+    if z.shape[0] != B * N or not z.is_contiguous():
+        raise ValueError(f"clip_pool_eos: z must be a contiguous [{B * N}, C] buffer")
+    if out is None:
+        out = torch.empty(B, C, dtype=BF16, device=z.device)
+    _chk(out, BF16, "clip_pool_eos.out", 2)
+    if tuple(out.shape) != (B, C) or not out.is_contiguous():
+        raise ValueError(f"clip_pool_eos: out must be a contiguous [{B}, {C}] buffer")
+    check(lib.ae_clip_pool_eos_bf16(_p(ids), 1 if ids.dtype == torch.int64 else 0, _p(z), _p(out), B, N, C, int(eos_token_id), _s()), "ae_clip_pool_eos_bf16")
+    return out
+
+
 # --------------------------------------------------------------------------- layout / elementwise
 def nchw_to_rows(x, c_pad=None):
     """[B,C,H,W] (fp32 or bf16) -> channels-last bf16 [B*H*W, Cpad] (zero padded channels)."""

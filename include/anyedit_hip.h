@@ -413,6 +413,29 @@ int ae_nms_sorted_f32(const float* boxes, void* keep, int N, float iou_threshold
 int ae_sam_preprocess_f32(const void* x, int x_is_u8, float* y, int B, int C, int h, int w, int S, const float* mean, const float* stdv,
                           void* stream);
 
+/* ---- CLIP text tower (ldm/modules/encoders/modules.py:107-150 FrozenCLIPEmbedder; ddpm.py:664-677 get_learned_conditioning;
+ * tools/global_tool.py:360-396 _encode_prompt; train.py:644 text_encoder(input_ids)[0]; cldm/hack.py:23-68 chunked forward).  The
+ * projections and LayerNorms of its 12 pre-LN layers are ae_gemm_bf16 / ae_layernorm_bf16 launches; these three are the rest.
+ * ae_attn_causal_short_bf16: out = softmax(causal(q k^T * scale)) v for the tower's self-attention (the causal mask of
+ *   transformers' CLIPTextTransformer).  q/k/v bf16 addressed through (batch, head, row) element strides as in ae_attn_fwd_bf16
+ *   (so a packed [B*N, 3*H*D] projection is read in place), out bf16 through its own strides.  1 <= N <= 128, D in {32, 64};
+ *   strides of q/k/v multiples of 8, of out multiples of 4; anything else is refused.  Row i attends keys [0, i]; row 0 returns v[0].
+ * ae_clip_embed_bf16: CLIPTextEmbeddings: out[b*N + n] = token_table[ids[b*N + n]] + position_table[n], tables and out bf16 rows of
+ *   C (C % 8 == 0).  ids int32 (ids_are_i64 = 0) or int64.  An id outside [0, vocab) is CLAMPED into the table by the kernel (the
+ *   host cannot range-check device ids without a synchronisation; host-side ids are checked by the caller).
+ * ae_bias_act_f32_bf16: the activation between CLIPMLP's fc1 and fc2: y = act(u + bias), u the fp32 product of
+ *   ae_gemm_bf16(..., out_f32 = 1), y bf16 — the pre-activation is never rounded to bf16.  act 0: quick-GELU t * sigmoid(1.702 t)
+ *   (OpenAI ViT-L/14), act 1: erf-GELU (SD-2's ViT-H text tower).  N % 4 == 0, row strides multiples of 4.                        */
+int ae_attn_causal_short_bf16(const void* q, const void* k, const void* v, void* out, int B, int H, int N, int D,
+                              long q_sb, long q_sh, long q_sn, long k_sb, long k_sh, long k_sn, long v_sb, long v_sh, long v_sn,
+                              long o_sb, long o_sh, long o_sn, float scale, void* stream);
+int ae_clip_embed_bf16(const void* ids, int ids_are_i64, const void* token_table, const void* position_table, void* out, int B, int N,
+                       int C, int vocab, int positions, void* stream);
+int ae_bias_act_f32_bf16(const float* u, long ldu, const float* bias, void* y, long ldy, long M, int N, int act, void* stream);
+/* pooler_output (modules.py:141-142 layer == "pooled"): out[b] = z[b, first n with ids[b, n] == eos_token_id] (n = 0 when there is none), z the
+ * final-normed bf16 [B, N, C], out bf16 [B, C]; the position is found on the device, so ids are not read back.                      */
+int ae_clip_pool_eos_bf16(const void* ids, int ids_are_i64, const void* z, void* out, int B, int N, int C, long eos_token_id, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
