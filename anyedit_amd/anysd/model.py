@@ -58,7 +58,11 @@ class MoE(nn.Module):
                  clip_dim=1280, ip_tokens=4):
         super().__init__()
         self.unet = unet
-        self.image_encoder = image_encoder  # CLIP vision tower: outside the hot path, the caller passes its hidden states
+        # CLIP vision tower (ldm/modules/encoders/clip_vision.py, train.py:404): frozen; `reference_embeds` runs it, or the caller passes its hidden states
+        enc_dim = getattr(image_encoder, "hidden_size", None)
+        if enc_dim is not None and enc_dim != clip_dim:
+            raise ValueError(f"MoE: the image encoder's hidden_size {enc_dim} does not match clip_dim {clip_dim} (image_proj_model reads hidden states of that width)")
+        self.image_encoder = image_encoder
         self.expert_num = expert_num
         self.context_dim = context_dim
         self.image_proj_model = ImageProjModel(clip_dim, context_dim, ip_tokens)
@@ -73,7 +77,7 @@ class MoE(nn.Module):
             self.load_state_dict(trusted_torch_load(ckpt_path, "cpu"), strict=False)
 
     def save_pretrained(self, path):
-        sd = {k: v for k, v in self.state_dict().items() if not k.startswith("unet.")}
+        sd = {k: v for k, v in self.state_dict().items() if not k.startswith(("unet.", "image_encoder."))}
         torch.save(sd, path)
 
     @torch.no_grad()
@@ -82,8 +86,19 @@ class MoE(nn.Module):
         return ops.task_gate(self.task_embs.detach(), edit_code, self.gate.weight.detach(), self.gate.bias.detach())
 
     @torch.no_grad()
+    def reference_embeds(self, pixel_values):
+        """train.py:689-691: image_encoder(reference_clip_images, output_hidden_states=True).hidden_states[-2] -> [B, N, clip_dim] bf16, a copy
+        the caller owns (the tower's own result is a static buffer).  pixel_values: [B, 3, S, S] on the GPU, normalised fp32 / bf16 or raw uint8."""
+        if self.image_encoder is None:
+            raise ValueError("MoE.reference_embeds: this MoE was built without an image_encoder (MoE(unet, image_encoder=CLIPVisionModelWithProjection(...)))")
+        return self.image_encoder.encode_pixels(pixel_values, -2).clone()
+
+    @torch.no_grad()
     def prepare_conditioning(self, encoder_hidden_states, ref_embeds, edit_code, ip_scale=None):
-        """Everything step-invariant, once per edit.  Returns (context_rows [B*(L+1), Dc], kv_cache dict)."""
+        """Everything step-invariant, once per edit.  Returns (context_rows [B*(L+1), Dc], kv_cache dict).  ref_embeds: [B, N, clip_dim] hidden
+        states, or 4-D pixel values [B, 3, S, S], which the image encoder turns into them first."""
+        if ref_embeds.dim() == 4:
+            ref_embeds = self.reference_embeds(ref_embeds)
         B, L, Dc = encoder_hidden_states.shape
         dev = encoder_hidden_states.device
         te = self.task_embs.detach()[edit_code.long()]                                   # [B, Dc] lookup (indexing = plumbing)

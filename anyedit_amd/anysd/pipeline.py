@@ -145,21 +145,28 @@ class EditPipeline:
         return self._null_ehs
 
     @torch.no_grad()
-    def edit_text(self, x_T, img_lat, prompts_or_ids, ref_embeds, edit_code, **edit_kwargs):
+    def edit_text(self, x_T, img_lat, prompts_or_ids, ref_embeds, edit_code, reference_images=None, **edit_kwargs):
         """`edit` from the instruction itself: prompts (needs the encoder's tokenizer) or [B, N] token ids are encoded by the HIP text tower,
-        the empty prompt comes from the cache, and the rest is `edit(x_T, img_lat, ehs, null_ehs, ref_embeds, edit_code, **edit_kwargs)`."""
+        the empty prompt comes from the cache, and the rest is `edit(x_T, img_lat, ehs, null_ehs, ref_embeds, edit_code, **edit_kwargs)`.
+        reference_images: as in `edit`."""
         if self.text_encoder is None:
             raise ValueError("edit_text: this pipeline was built without a text_encoder (EditPipeline(..., text_encoder=FrozenCLIPEmbedder(...)))")
         null_ehs = self.null_prompt_ehs()
         ehs = self.text_encoder.encode_ids(self._prompt_ids(prompts_or_ids))
-        return self.edit(x_T, img_lat, ehs, null_ehs, ref_embeds, edit_code, **edit_kwargs)
+        return self.edit(x_T, img_lat, ehs, null_ehs, ref_embeds, edit_code, reference_images=reference_images, **edit_kwargs)
 
     @torch.no_grad()
     def edit(self, x_T, img_lat, ehs, null_ehs, ref_embeds, edit_code, steps=50, s_txt=7.5, s_img=1.5, eta=0.0, mask=None,
-             x0=None, prepared=False, step_callback=None):
-        """Returns the edited latents [B,4,h,w] fp32.  mask/x0: optional masked-latent blend (global_tool.py:183-184)."""
+             x0=None, prepared=False, step_callback=None, reference_images=None):
+        """Returns the edited latents [B,4,h,w] fp32.  mask/x0: optional masked-latent blend (global_tool.py:183-184).
+        reference_images: [B, 3, S, S] pixel values for the visual edit types, instead of `ref_embeds` (pass None there): the MoE's image
+        encoder turns them into the penultimate hidden states (train.py:689-691); the CFG layout of `prepare` is unchanged."""
         B, C = x_T.shape[0], x_T.shape[1]
         dev = x_T.device
+        if reference_images is not None:
+            if ref_embeds is not None:
+                raise ValueError("edit: pass ref_embeds or reference_images, not both")
+            ref_embeds = self.moe.reference_embeds(reference_images)
         if not prepared:
             self.prepare(img_lat, ehs, null_ehs, ref_embeds, edit_code)
         s = self.sampler

@@ -57,8 +57,11 @@ class AnySDTrainer:
     def forward_loss(self, latents, image_cond, encoder_hidden_states, ref_embeds, edit_code, noise, timesteps, null_ehs=None,
                      dropout_u=None, dropout_p=0.05):
         """Returns (loss scalar tensor, tape, leaves) with the forward recorded; call `backward` next.  `encoder_hidden_states`: [B, L, Dc] hidden
-        states, or — with a `text_encoder` — the [B, N] token ids they are encoded from."""
+        states, or — with a `text_encoder` — the [B, N] token ids they are encoded from.  `ref_embeds`: [B, N, clip_dim] hidden states, or 4-D
+        `reference_clip_images` [B, 3, S, S] (train.py:683-691), encoded by the MoE's frozen image encoder outside the tape."""
         moe, dev = self.moe, latents.device
+        if ref_embeds.dim() == 4:
+            ref_embeds = moe.reference_embeds(ref_embeds)
         B = latents.shape[0]
         sa, s1 = self.sqrt_ac.to(dev)[timesteps], self.sqrt_1mac.to(dev)[timesteps]
         noisy = ops.q_sample(latents.float(), noise.float(), sa, s1)

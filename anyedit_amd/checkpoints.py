@@ -211,6 +211,26 @@ def text_encoder_state_dict(embedder, sd):
     return hit
 
 
+def load_clip_vision(tower, path_or_state_dict, location="cpu"):
+    """Fills a `CLIPVisionModelWithProjection` (train.py:404 `from_pretrained(args.image_encoder_path)`) from a file or a state dict.
+    Recognised forms: the Hugging Face layout (`vision_model.*`, `visual_projection.weight`), the same under an `image_encoder.` prefix (keys
+    outside that prefix are ignored then), and the form without the `vision_model.` level (`embeddings.*`, `pre_layrnorm.*`, `encoder.*`,
+    `post_layernorm.*`).  Missing or unexpected keys are reported as `load_state_dict(strict=True)` reports them.  Returns the form found."""
+    sd = path_or_state_dict
+    if not isinstance(sd, dict):
+        from anyedit_amd.cldm.model import load_state_dict
+        sd = load_state_dict(sd, location)
+    layout = "huggingface"
+    if any(k.startswith("image_encoder.") for k in sd):
+        sd = {k[len("image_encoder."):]: v for k, v in sd.items() if k.startswith("image_encoder.")}
+        layout = "image_encoder"
+    if not any(k.startswith("vision_model.") for k in sd):
+        sd = {(k if k.startswith("visual_projection.") else "vision_model." + k): v for k, v in sd.items()}
+        layout += "-flat"
+    tower.load_state_dict(sd, strict=True)
+    return layout
+
+
 def load_sd_checkpoint(path, unet=None, vae=None, text_encoder=None, location="cpu"):
     """`load_unet_weights`' sibling for a FULL SD-1.5 state dict (CompVis lineage): routes `model.diffusion_model.*` to `unet`,
     `first_stage_model.*` to `vae` and `cond_stage_model.*` to `text_encoder` (a FrozenCLIPEmbedder); a part given as None is skipped.

@@ -909,6 +909,98 @@ def clip_pool_eos(ids, z, eos_token_id, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- CLIP vision tower (csrc/clip_vision.hip)
+_PX_DTYPES = {torch.float32: 0, BF16: 1, torch.uint8: 2}
+
+
+def clip_patch_kpad(Cin, P):
+    """Columns of a patch row: Cin * P * P rounded up to a multiple of 64 (P = 14: 588 -> 640)."""
+    return (Cin * P * P + 63) // 64 * 64
+
+
+def pack_patch_embedding(w):
+    """CLIPVisionEmbeddings.patch_embedding.weight [C, Cin, P, P] -> bf16 [C, Kpad]: flattened, zero-padded to `clip_patch_kpad` columns
+    (the weight image that goes with `clip_patch_rows`)."""
+    C, Cin, P, P2 = w.shape
+    if P != P2:
+        raise ValueError(f"pack_patch_embedding: square patches only, got {P}x{P2}")
+    out = torch.zeros(C, clip_patch_kpad(Cin, P), dtype=BF16, device=w.device)
+    out[:, :Cin * P * P] = w.detach().reshape(C, -1).to(BF16)
+    return out
+
+
+def clip_patch_rows(x, P, rescale=1.0, mean=None, std=None, out=None):
+    """im2col of the CLIP patch embedding with the image processor's rescale + normalise fused in: x [B, Cin, H, W] (fp32, bf16 or uint8,
+    contiguous, H % P == W % P == 0) -> bf16 rows [B*(H/P)*(W/P), Kpad]; column c*P*P + ky*P + kx = (x * rescale - mean[c]) / std[c]
+    (mean = std = None: x * rescale), pad columns written as zeros."""
+    if not x.is_cuda:
+        raise ValueError("clip_patch_rows.x: expected a GPU tensor (anyedit_amd has no CPU path)")
+    if x.dtype not in _PX_DTYPES or x.dim() != 4 or not x.is_contiguous():
+        raise TypeError(f"clip_patch_rows.x: expected a contiguous fp32 / bf16 / uint8 [B, Cin, H, W] tensor, got {x.dtype} {tuple(x.shape)}")
+    B, Cin, H, W = x.shape
+    if P <= 0 or H % P or W % P:
+        raise ValueError(f"clip_patch_rows: image {H}x{W} is not a whole number of {P}x{P} patches")
+    if (mean is None) != (std is None):
+        raise ValueError("clip_patch_rows: mean and std go together")
+    if mean is not None:
+        _chk(mean, torch.float32, "clip_patch_rows.mean", 1)
+        _chk(std, torch.float32, "clip_patch_rows.std", 1)
+        if mean.numel() != Cin or std.numel() != Cin or not mean.is_contiguous() or not std.is_contiguous():
+            raise ValueError(f"clip_patch_rows: mean and std need one value per channel ({Cin})")
+    M, Kpad = B * (H // P) * (W // P), clip_patch_kpad(Cin, P)
+    if out is None:
+        out = torch.empty(M, Kpad, dtype=BF16, device=x.device)
+    _chk(out, BF16, "clip_patch_rows.out", 2)
+    if tuple(out.shape) != (M, Kpad) or not out.is_contiguous():
+        raise ValueError(f"clip_patch_rows: out must be a contiguous [{M}, {Kpad}] buffer")
+    check(lib.ae_clip_patch_rows_bf16(_p(x), _PX_DTYPES[x.dtype], _p(out), B, Cin, H, W, P, Kpad, float(rescale), _p(mean), _p(std), _s()),
+          "ae_clip_patch_rows_bf16")
+    return out
+
+
+def clip_vision_embed_ln(patch, class_embedding, pos, gamma, beta, eps, B, out=None):
+    """Token rows + pre_layrnorm of the CLIP vision tower in one launch: out[b, 0] = LN(class_embedding + pos[0]), out[b, 1 + i] =
+    LN(patch[b*G + i] + pos[1 + i]) -> bf16 [B*(1+G), C].  patch: the fp32 [B*G, C] product of `gemm(rows, Wpatch, out_f32=True)`;
+    class_embedding [C], pos [1+G, C], gamma / beta [C] fp32.  C % 8 == 0, C <= 2048."""
+    _chk(patch, torch.float32, "clip_vision_embed_ln.patch", 2)
+    _chk(class_embedding, torch.float32, "clip_vision_embed_ln.class_embedding", 1)
+    _chk(pos, torch.float32, "clip_vision_embed_ln.pos", 2)
+    _chk(gamma, torch.float32, "clip_vision_embed_ln.gamma", 1)
+    _chk(beta, torch.float32, "clip_vision_embed_ln.beta", 1)
+    M, C = patch.shape
+    if B <= 0 or M % B:
+        raise ValueError(f"clip_vision_embed_ln: {M} patch rows do not split into {B} samples")
+    G = M // B
+    if patch.stride(1) != 1 or tuple(pos.shape) != (G + 1, C) or not pos.is_contiguous() or class_embedding.numel() != C or gamma.numel() != C or beta.numel() != C:
+        raise ValueError(f"clip_vision_embed_ln: need patch rows of unit inner stride, pos [{G + 1}, {C}] contiguous and class_embedding / gamma / beta of {C} values")
+    if out is None:
+        out = torch.empty(B * (G + 1), C, dtype=BF16, device=patch.device)
+    _chk(out, BF16, "clip_vision_embed_ln.out", 2)
+    if tuple(out.shape) != (B * (G + 1), C) or not out.is_contiguous():
+        raise ValueError(f"clip_vision_embed_ln: out must be a contiguous [{B * (G + 1)}, {C}] buffer")
+    check(lib.ae_clip_vision_embed_ln_bf16(_p(patch), patch.stride(0), _p(class_embedding), _p(pos), _p(gamma), _p(beta), _p(out), B, G, C, float(eps), _s()),
+          "ae_clip_vision_embed_ln_bf16")
+    return out
+
+
+def clip_vision_pool_ln(x, N, gamma, beta, eps, out=None):
+    """post_layernorm of the class rows only: x bf16 [B*N, C] contiguous -> LN(x[b*N]) as bf16 [B, C] (the other rows are not read)."""
+    _chk(x, BF16, "clip_vision_pool_ln.x", 2)
+    _chk(gamma, torch.float32, "clip_vision_pool_ln.gamma", 1)
+    _chk(beta, torch.float32, "clip_vision_pool_ln.beta", 1)
+    M, C = x.shape
+    if N <= 0 or M % N or not x.is_contiguous() or gamma.numel() != C or beta.numel() != C:
+        raise ValueError(f"clip_vision_pool_ln: x must be a contiguous [B*{N}, C] buffer with gamma / beta of C values, got {tuple(x.shape)}")
+    B = M // N
+    if out is None:
+        out = torch.empty(B, C, dtype=BF16, device=x.device)
+    _chk(out, BF16, "clip_vision_pool_ln.out", 2)
+    if tuple(out.shape) != (B, C) or not out.is_contiguous():
+        raise ValueError(f"clip_vision_pool_ln: out must be a contiguous [{B}, {C}] buffer")
+    check(lib.ae_clip_vision_pool_ln_bf16(_p(x), N * C, _p(gamma), _p(beta), _p(out), B, C, float(eps), _s()), "ae_clip_vision_pool_ln_bf16")
+    return out
+
+
 # --------------------------------------------------------------------------- layout / elementwise
 def nchw_to_rows(x, c_pad=None):
     """[B,C,H,W] (fp32 or bf16) -> channels-last bf16 [B*H*W, Cpad] (zero padded channels)."""

@@ -436,6 +436,29 @@ int ae_bias_act_f32_bf16(const float* u, long ldu, const float* bias, void* y, l
  * final-normed bf16 [B, N, C], out bf16 [B, C]; the position is found on the device, so ids are not read back.                      */
 int ae_clip_pool_eos_bf16(const void* ids, int ids_are_i64, const void* z, void* out, int B, int N, int C, long eos_token_id, void* stream);
 
+/* ---- CLIP vision tower (train.py:404 CLIPVisionModelWithProjection.from_pretrained(image_encoder_path); train.py:689-691
+ * image_encoder(reference_clip_images, output_hidden_states=True).hidden_states[-2]).  The projections, layer LayerNorms, fc1 activation and
+ * the non-causal attention of its pre-LN layers are ae_gemm_bf16 / ae_layernorm_bf16 / ae_bias_act_f32_bf16 / ae_attn_fwd_bf16 launches;
+ * these three are the rest.  All write bf16 with one rounding at the store, keep fp32 statistics, use no scratch and no atomics.
+ * ae_clip_patch_rows_bf16: the im2col of CLIPVisionEmbeddings.patch_embedding (Conv2d(Cin, C, P, stride P, bias=False)) with the image
+ *   processor's rescale + normalise fused in.  x: contiguous [B, Cin, H, W], x_dtype 0 fp32 / 1 bf16 / 2 uint8, H % P == 0, W % P == 0.
+ *   rows: bf16 [B*(H/P)*(W/P), Kpad], Kpad = Cin*P*P rounded up to a multiple of 64; column c*P*P + ky*P + kx of row (b, gy, gx) holds
+ *   (x[b, c, gy*P + ky, gx*P + kx] * rescale - mean[c]) / std[c]; mean = std = NULL: x * rescale (rescale = 1: plain conversion).  Columns
+ *   [Cin*P*P, Kpad) are WRITTEN as zeros.  The matching weight image is the conv weight flattened to [C, Cin*P*P], zero-padded to Kpad.
+ *   x needs only the alignment of its type (a P = 14 patch row of fp32 pixels is 8-byte aligned); wider loads are taken when P % 8 == 0.
+ * ae_clip_vision_embed_ln_bf16: the token rows and pre_layrnorm in one launch: out[b*(1+G)] = LN(class_embedding + pos[0]),
+ *   out[b*(1+G) + 1 + i] = LN(patch[(b*G + i) * ldp ...] + pos[1 + i]); patch is the fp32 product of ae_gemm_bf16(rows, Wpatch, out_f32 = 1),
+ *   class_embedding [C] and pos [1+G, C] fp32, out bf16 [B*(1+G), C] (transformers' hidden_states[0]).  The un-normalised sum is never stored.
+ *   C % 8 == 0, C <= 2048 (refused above), ldp % 4 == 0, pointers 16-byte aligned.
+ * ae_clip_vision_pool_ln_bf16: post_layernorm of the class rows only: out[b] = LN(x[b * row_stride ...]), x bf16 (row_stride = N*C picks
+ *   row b*N of a [B*N, C] buffer), out bf16 [B, C].  C % 8 == 0, C <= 2048, row_stride % 8 == 0.                                         */
+int ae_clip_patch_rows_bf16(const void* x, int x_dtype, void* rows, int B, int Cin, int H, int W, int P, int Kpad, float rescale,
+                            const float* mean, const float* stdv, void* stream);
+int ae_clip_vision_embed_ln_bf16(const float* patch, long ldp, const float* class_embedding, const float* pos, const float* gamma,
+                                 const float* beta, void* out, int B, int G, int C, float eps, void* stream);
+int ae_clip_vision_pool_ln_bf16(const void* x, long row_stride, const float* gamma, const float* beta, void* out, int B, int C, float eps,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif
