@@ -231,6 +231,31 @@ def load_clip_vision(tower, path_or_state_dict, location="cpu"):
     return layout
 
 
+def load_dinov2(module, path_or_state_dict, location="cpu"):
+    """Fills a `DinoVisionTransformer` or a `FrozenDinoV2Encoder` (modules.py:285-287 `dinov2.load_state_dict(torch.load(DINOv2_weight_path))`)
+    from a file or a state dict.  Recognised forms: a bare DINOv2 file (`cls_token`, `pos_embed`, `blocks.N.*` ...: `dinov2_vit*14_pretrain.pth`)
+    into the tower or into the encoder's `.model` (its projector is left as it is); an AnyDoor checkpoint's `cond_stage_model.`-prefixed entries
+    (keys outside that prefix are ignored then) and the flat `model.*` / `projector.*` dict, both into the encoder.  Missing or unexpected
+    keys are reported as `load_state_dict(strict=True)` reports them.  Returns the form found."""
+    from anyedit_amd.ldm.modules.encoders.dino_vision import FrozenDinoV2Encoder
+    sd = path_or_state_dict
+    if not isinstance(sd, dict):
+        from anyedit_amd.cldm.model import load_state_dict
+        sd = load_state_dict(sd, location)
+    encoder = isinstance(module, FrozenDinoV2Encoder)
+    layout = "encoder"
+    if any(k.startswith("cond_stage_model.") for k in sd):
+        sd = {k[len("cond_stage_model."):]: v for k, v in sd.items() if k.startswith("cond_stage_model.")}
+        layout = "cond_stage_model"
+    if any(k.startswith(("model.", "projector.")) for k in sd):
+        if not encoder:
+            raise ValueError(f"load_dinov2: the state dict holds an encoder ({layout}: model.* / projector.*); pass a FrozenDinoV2Encoder, or its .model with a bare DINOv2 file")
+        module.load_state_dict(sd, strict=True)
+        return layout
+    (module.model if encoder else module).load_state_dict(sd, strict=True)
+    return "dinov2"
+
+
 def load_sd_checkpoint(path, unet=None, vae=None, text_encoder=None, location="cpu"):
     """`load_unet_weights`' sibling for a FULL SD-1.5 state dict (CompVis lineage): routes `model.diffusion_model.*` to `unet`,
     `first_stage_model.*` to `vae` and `cond_stage_model.*` to `text_encoder` (a FrozenCLIPEmbedder); a part given as None is skipped.

@@ -149,28 +149,32 @@ class LatentDiffusion(DDPM):
         self.first_stage_model = vae.eval().requires_grad_(False)
 
     def instantiate_cond_stage(self, config):
-        """ddpm.py:622-640, frozen branch.  A config whose target resolves to this package's FrozenCLIPEmbedder (the CLIP text tower on HIP) or
-        an already built one is installed frozen; the two placeholder strings and every other target leave `cond_stage_model = None` (the
-        caller then passes encoder hidden states, as before)."""
+        """ddpm.py:622-640, frozen branch.  A config whose target resolves to one of this package's encoders — FrozenCLIPEmbedder (the CLIP text
+        tower on HIP) or FrozenDinoV2Encoder (the DINOv2 image encoder on HIP, anydoor.yaml's cond stage) — or an already built one is installed
+        frozen; the two placeholder strings and every other target leave `cond_stage_model = None` (the caller then passes encoder hidden states,
+        as before).  anydoor.yaml's `weight:` key (a checkpoint path the reference opens at import time) is accepted and not opened: the
+        weights come from the state dict, `checkpoints.load_dinov2`."""
         from anyedit_amd.ldm.modules.encoders.modules import FrozenCLIPEmbedder
+        from anyedit_amd.ldm.modules.encoders.dino_vision import FrozenDinoV2Encoder
         from anyedit_amd.ldm.util import get_obj_from_str
+        known = (FrozenCLIPEmbedder, FrozenDinoV2Encoder)
         model = None
-        if isinstance(config, FrozenCLIPEmbedder):
+        if isinstance(config, known):
             model = config
         elif isinstance(config, dict) and "target" in config:
             try:
                 cls = get_obj_from_str(config["target"])
             except (ImportError, AttributeError):
                 cls = None
-            if cls is FrozenCLIPEmbedder:
-                model = cls(**config.get("params", {}))
+            if cls in known:
+                model = cls(**(config.get("params") or {}))
         self.cond_stage_model = None if model is None else model.eval().requires_grad_(False)
 
     def get_learned_conditioning(self, c):
         """ddpm.py:664-677."""
         if self.cond_stage_model is None:
             raise RuntimeError("get_learned_conditioning: this LatentDiffusion has no cond stage (cond_stage_config was None, a placeholder or a "
-                               "target other than FrozenCLIPEmbedder): pass the encoder hidden states yourself")
+                               "target other than FrozenCLIPEmbedder / FrozenDinoV2Encoder): pass the encoder hidden states yourself")
         if self.cond_stage_forward is None:
             if hasattr(self.cond_stage_model, 'encode') and callable(self.cond_stage_model.encode):
                 return self.cond_stage_model.encode(c)

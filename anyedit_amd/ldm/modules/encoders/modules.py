@@ -295,3 +295,12 @@ class FrozenCLIPEmbedder(AbstractEncoder):
 
     def encode(self, text):
         return self(text)
+
+
+def __getattr__(name):
+    """`ldm.modules.encoders.modules.FrozenDinoV2Encoder` (anydoor.yaml's cond_stage_config target; modules.py:279-315) lives in dino_vision.py,
+    which imports this module: resolved on first use."""
+    if name == "FrozenDinoV2Encoder":
+        from anyedit_amd.ldm.modules.encoders.dino_vision import FrozenDinoV2Encoder
+        return FrozenDinoV2Encoder
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

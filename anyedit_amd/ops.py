@@ -1001,6 +1001,49 @@ def clip_vision_pool_ln(x, N, gamma, beta, eps, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- DINOv2 image encoder (csrc/dino_vision.hip)
+def dino_embed(patch, patch_bias, cls_token, pos, B, out=None):
+    """Token rows of DinoVisionTransformer (prepare_tokens_with_masks): out[b, 0] = cls_token + pos[0], out[b, 1 + i] = patch[b*G + i] +
+    patch_bias + pos[1 + i] -> bf16 [B*(1+G), C], rounded once.  patch: the fp32 [B*G, C] product of `gemm(rows, Wpatch, out_f32=True)` (row
+    stride free); patch_bias / cls_token [C], pos [1+G, C] fp32 (the table interpolated to this grid).  No LayerNorm.  C % 8 == 0."""
+    _chk(patch, torch.float32, "dino_embed.patch", 2)
+    _chk(patch_bias, torch.float32, "dino_embed.patch_bias", 1)
+    _chk(cls_token, torch.float32, "dino_embed.cls_token", 1)
+    _chk(pos, torch.float32, "dino_embed.pos", 2)
+    M, C = patch.shape
+    if B <= 0 or M % B:
+        raise ValueError(f"dino_embed: {M} patch rows do not split into {B} samples")
+    G = M // B
+    if patch.stride(1) != 1 or tuple(pos.shape) != (G + 1, C) or not pos.is_contiguous() or cls_token.numel() != C or patch_bias.numel() != C:
+        raise ValueError(f"dino_embed: need patch rows of unit inner stride, pos [{G + 1}, {C}] contiguous and cls_token / patch_bias of {C} values")
+    if out is None:
+        out = torch.empty(B * (G + 1), C, dtype=BF16, device=patch.device)
+    _chk(out, BF16, "dino_embed.out", 2)
+    if tuple(out.shape) != (B * (G + 1), C) or not out.is_contiguous():
+        raise ValueError(f"dino_embed: out must be a contiguous [{B * (G + 1)}, {C}] buffer")
+    check(lib.ae_dino_embed_bf16(_p(patch), patch.stride(0), _p(patch_bias), _p(cls_token), _p(pos), _p(out), B, G, C, _s()), "ae_dino_embed_bf16")
+    return out
+
+
+def swiglu(u, bias, out=None):
+    """y[m, j] = silu(u[m, j] + bias[j]) * (u[m, Hd + j] + bias[Hd + j]) as bf16, u the fp32 [M, 2*Hd] product of `gemm(..., out_f32=True)` with
+    SwiGLUFFN's w12 (row stride free): the pre-activation is never rounded.  out: [M, Hd] bf16 with unit inner stride; where its row stride
+    is wider than Hd, the columns between Hd and the stride are written as zeros.  Hd % 8 == 0."""
+    _chk(u, torch.float32, "swiglu.u", 2)
+    _chk(bias, torch.float32, "swiglu.bias", 1)
+    M, N2 = u.shape
+    if N2 % 2 or u.stride(1) != 1 or bias.numel() != N2 or not bias.is_contiguous():
+        raise ValueError("swiglu: u needs an even number of columns and unit inner stride, bias one value per column")
+    Hd = N2 // 2
+    if out is None:
+        out = torch.empty(M, Hd, dtype=BF16, device=u.device)
+    _chk(out, BF16, "swiglu.out", 2)
+    if tuple(out.shape) != (M, Hd) or out.stride(1) != 1:
+        raise ValueError(f"swiglu: out must be [{M}, {Hd}] with unit inner stride")
+    check(lib.ae_swiglu_f32_bf16(_p(u), u.stride(0), _p(bias), _p(out), out.stride(0), M, Hd, _s()), "ae_swiglu_f32_bf16")
+    return out
+
+
 # --------------------------------------------------------------------------- layout / elementwise
 def nchw_to_rows(x, c_pad=None):
     """[B,C,H,W] (fp32 or bf16) -> channels-last bf16 [B*H*W, Cpad] (zero padded channels)."""

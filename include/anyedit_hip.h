@@ -459,6 +459,25 @@ int ae_clip_vision_embed_ln_bf16(const float* patch, long ldp, const float* clas
 int ae_clip_vision_pool_ln_bf16(const void* x, long row_stride, const float* gamma, const float* beta, void* out, int B, int C, float eps,
                                 void* stream);
 
+/* ---- DINOv2 image encoder (ldm/modules/encoders/modules.py:279-315 FrozenDinoV2Encoder: dinov2_vitg14 forward_features, class + patch tokens
+ * after the final norm, projector = Linear(1536, 1024); the backbone is AnyEdit_Collection/other_modules/depth_anything_v2/dinov2.py:44-328
+ * DinoVisionTransformer).  The patch im2col is ae_clip_patch_rows_bf16 (ImageNet mean / std), everything in the blocks is ae_gemm_bf16 /
+ * ae_layernorm_bf16 / ae_attn_fwd_bf16 / ae_bias_act_f32_bf16, LayerScale (dinov2_layers/layer_scale.py) is folded into the weights at pack
+ * time; these two are the rest.  Both write bf16 with one rounding at a 16-byte store, use no scratch and no atomics.
+ * ae_dino_embed_bf16: the token rows (dinov2.py:212-219 prepare_tokens_with_masks, no masks, no register tokens):
+ *   out[b*(1+G)] = cls_token + pos[0], out[b*(1+G) + 1 + i] = patch[(b*G + i) * ldp ...] + patch_bias + pos[1 + i]; patch is the fp32 product of
+ *   ae_gemm_bf16(rows, Wpatch, out_f32 = 1), patch_bias / cls_token [C] and pos [1+G, C] fp32 (pos: dinov2.py:179-210 interpolate_pos_encoding
+ *   for this grid, made on the host side once), out bf16 [B*(1+G), C].  No LayerNorm: DINOv2 has no pre-norm.  C % 8 == 0, ldp % 4 == 0,
+ *   pointers 16-byte aligned.
+ * ae_swiglu_f32_bf16: the gate of SwiGLUFFN (dinov2_layers/swiglu_ffn.py:29-33: x1, x2 = w12(x).chunk(2); silu(x1) * x2):
+ *   y[m*ldy + j] = silu(u[m*ldu + j] + bias[j]) * (u[m*ldu + Hd + j] + bias[Hd + j]) for j < Hd, u the fp32 [M, 2*Hd] product of
+ *   ae_gemm_bf16(..., out_f32 = 1) — the pre-activation is never rounded —, bias fp32 [2*Hd], y bf16.  Columns [Hd, ldy) of y are WRITTEN as
+ *   zeros (a padded contraction width for w3 contracts against zeros).  Hd % 8 == 0, ldu % 4 == 0, ldu >= 2*Hd, ldy % 8 == 0, ldy >= Hd,
+ *   pointers 16-byte aligned.                                                                                                              */
+int ae_dino_embed_bf16(const float* patch, long ldp, const float* patch_bias, const float* cls_token, const float* pos, void* out, int B, int G,
+                       int C, void* stream);
+int ae_swiglu_f32_bf16(const float* u, long ldu, const float* bias, void* y, long ldy, long M, int Hd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
