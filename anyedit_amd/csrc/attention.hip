@@ -540,8 +540,8 @@ extern "C" int ae_attn_fwd_bf16(const void* q, const void* k, const void* v, voi
     a.lse = lse; a.lse2 = lse2;
     if (lse2) AE_REQUIRE(k2 != nullptr, "ae_attn_fwd_bf16: lse2 needs a second segment");
     hipStream_t s = (hipStream_t)stream;
-    // long-sequence / plain-softmax shapes (UNet self- and cross-attention at head_dim 40 / 80) go to the 32x32x16 kernel of
-    // attention_fast.hip; everything it does not cover (bias, masks, log-sum-exp outputs, other head dims) stays here.
+    // head dims 40 / 80 / 160 go to the 32x32x16 kernels of attention_fast.hip (plain softmax, a second segment, out_scale / accumulate, the
+    // rel-pos bias forms it lists); they write lse / lse2 themselves.  What it declines (key masks, other head dims and bias shapes) stays here.
     static const int use_fast = env_int("AE_ATTN_FAST", 1);  // tuning knob: 0 = general kernel only (A/B)
     if (use_fast) {
         const int rc = ae_attn_fast_launch(a, D, s);

@@ -747,16 +747,19 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
 
 # --------------------------------------------------------------------------- attention
 def attention(q, k, v, B, H, Nq, Nk, D, scale, q_strides, k_strides, v_strides, out=None, rel_h=None, rel_w=None,
-              kH=0, kW=0, key_mask=None, out_scale=None, accumulate=False, seg2=None, lse=None, lse2=None):
-    """q/k/v: bf16 tensors (any shape) addressed via (batch, head, row) element strides; out: [B, Nq, H*D] bf16.
+              kH=0, kW=0, key_mask=None, out_scale=None, accumulate=False, seg2=None, lse=None, lse2=None, o_strides=None):
+    """q/k/v: bf16 tensors (any shape) addressed via (batch, head, row) element strides; out: [B, Nq, H*D] bf16, or any bf16 buffer
+    addressed through o_strides = (batch, head, row) element strides (multiples of 4).
     seg2 = (k2, v2, Nk2, k2_strides, v2_strides, scale2 [B] fp32): second key/value segment with its own softmax.
-    lse / lse2: optional fp32 [B, H, Nq] outputs (log2-domain log-sum-exp per segment) kept for attention_bwd."""
+    lse / lse2: optional contiguous fp32 [B, H, Nq] outputs kept for attention_bwd: the log2-domain log-sum-exp of each segment's own
+    logits, log2 sum_j exp(scale q.k_j [+ bias]).  They do not depend on out_scale, scale2 or accumulate (those act on the output only)."""
     if _TAPE is not None and _TAPE.active:
         return _TAPE.attention(q, k, v, B, H, Nq, Nk, D, scale, q_strides, k_strides, v_strides, out=out, key_mask=key_mask,
                                out_scale=out_scale, accumulate=accumulate, seg2=seg2, rel_h=rel_h)
     if out is None:
         out = torch.empty(B, Nq, H * D, dtype=BF16, device=q.device)
-    o_strides = (Nq * H * D, D, H * D)
+    if o_strides is None:
+        o_strides = (Nq * H * D, D, H * D)
     if seg2 is not None:
         k2, v2, Nk2, k2_strides, v2_strides, scale2 = seg2
         seg_args = (_p(k2), _p(v2), Nk2, *k2_strides, *v2_strides, _p(scale2))
@@ -795,12 +798,17 @@ def attention_fp8(q, k, v, B, H, Nq, Nk, D, scale, q_strides, k_strides, v_strid
 
 
 def attention_bwd(q, k, v, dout, lse, B, H, Nq, Nk, D, scale, q_strides, k_strides, v_strides, dq, dk, dv, dq_strides,
-                  dk_strides, dv_strides, out_scale=None, accumulate_dq=False, out=None, split_dkv=True):
+                  dk_strides, dv_strides, out_scale=None, accumulate_dq=False, out=None, split_dkv=True, o_strides=None, delta=None):
     """Gradients of one attention segment (ae_attn_bwd_bf16).  dq/dk/dv: bf16 tensors written through the given element strides
     (dk = dv = None when the key/value side needs no gradient).  out: the forward output [B, Nq, H*D] when it is this segment's alone
-    (lets the kernel take delta = rowsum(dout o out) up front).  Returns delta [B, H, Nq] fp32."""
-    delta = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
-    o_strides = (Nq * H * D, D, H * D)
+    (lets the kernel take delta = rowsum(dout o out) up front).  dout (and out) are [B, Nq, H*D], or addressed through o_strides =
+    (batch, head, row) element strides (multiples of 8).  lse: the forward's contiguous fp32 [B, H, Nq] log-sum-exp of this segment.
+    Returns delta, contiguous fp32 [B, H, Nq] (written into `delta` when given): rowsum(P o dP) with the un-scaled dout — like lse it
+    does not depend on out_scale (the gate scales dq / dk / dv only); summed over heads and rows it is the gradient of out_scale[b]."""
+    if delta is None:
+        delta = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+    if o_strides is None:
+        o_strides = (Nq * H * D, D, H * D)
     zero3 = (0, 0, 0)
     ws = None
     if dk is not None and split_dkv:   # few-key segments (cross-attention): the dK / dV pass cuts its query tiles across blocks through fp32 partials

@@ -6,7 +6,8 @@ directions, so an instantiation that is added or removed fails here until someon
 
 GPU: tools/route_check.py in a fresh child process with every AE_* variable removed from its environment (this test session itself runs
 with AE_ROWPANEL_ANY_M=1, set by test_hip_ops.py): every case must reach its declared instantiations, pass the element-wise float64
-check, leave its guard areas untouched and repeat bit for bit; every `default` ledger row must be reached by each case it lists.
+check, leave its guard areas untouched and repeat bit for bit; every `default` ledger row must be reached by each case it lists.  Every
+attention case also carries the log-sum-exp outputs through the same checks and reports their worst error / bound as `lse_ratio`.
 """
 import json
 import os
@@ -100,4 +101,8 @@ def test_route_cases_on_gpu():
     assert not failed, failed
     unreached = [(k, c) for k, (kind, cases) in RC.LEDGER.items() if kind == "default" for c in cases if k not in results[c]["keys"]]
     assert not unreached, unreached
+    attn = [c["id"] for c in RC.CASES if c["op"] == "attn"]
+    no_lse = [i for i in attn if not isinstance(results[i].get("lse_ratio"), float) or not results[i]["lse_ratio"] <= 1.0]
+    assert not no_lse, f"attention cases without a checked log-sum-exp: {no_lse}"
+    print("lse_ratio per attention case: " + ", ".join(f"{i} {results[i]['lse_ratio']:.3f}" for i in attn))
     assert p.returncode == 0, p.stderr[-4000:]

@@ -25,6 +25,23 @@ activation's slope (|gelu'| <= 1.13).  LayerNorm fold: a * rstd * (|x| |W| + |me
 STORED bf16 output per slab, |got - ref| <= a * sum|y| (resp. sum y^2) + 1e-30.  Attention: 2^-8 |ref| + 2^-8 * sum_j p_j |v_j| — the
 probabilities enter the PV product as bf16 (half an ulp each), the logits and the normalisation are fp32.
 
+Bound, log-sum-exp.  Every attention case also asks for `lse` (and `lse2` when it has a second segment) in the launches above: fp32
+[B, H, Nq], L2 = log2 sum_j exp(S_j) with S the logits in natural units (scale q.k + rel-pos bias; for lse2 the second segment's own
+logits with the same scale — scale2 is the gate on the output and does not enter).  The buffers sit between guards like the output, must
+repeat bit for bit and must hold no sentinel afterwards (every (b, h, q) was written).  On the checked (batch, head) pairs and query rows
+    |got - L2| <= log2(e) * (2^-8 + (a + 2^-9) * scale * max_j sum_d |q_d| |k_jd| + [rel-pos only] 2^-9 (max|rel_h| + max|rel_w|))
+                  + 2^-22 |L2| + 1e-6.
+The log-sum-exp is 1-Lipschitz in the sup-norm of the logits, so a per-logit error enters once, whatever the number of keys: the a-term
+is the fp32 accumulation of a logit (the constant of the output bound), the bias term the bf16 bias operands of the BIAS 3 route (as in
+the output bound).  2^-9 scale sum_d |q_d| |k_jd|: every kernel of attention_fast.hip multiplies Q by scale log2(e) ONCE and rounds the
+product to bf16 for the logit MFMA (its header, "Q is pre-multiplied"; load_q: pack_bf16x2(q * c)), half an ulp = 2^-9 relative per
+factor, so a logit is off by up to 2^-9 of its absolute products.  (Measured without this term on the MI355X: the short-K/V two-segment
+routes reached 1.7 times the bound on a second segment of 8 or 16 keys, where nothing averages the rounding out, and every other route
+0.12 - 0.98.)  2^-8: the fast kernels' denominator is a row of the PV MFMA, i.e. a sum of bf16-rounded probabilities — each within
+2^-8 relative (round-to-nearest: half an ulp; a truncating conversion is within one ulp, 2^-8 relative on average over a binade), all
+non-negative, so their sum is too, and |log(1 + x)| <= |x| / (1 - |x|); the general kernel sums fp32 probabilities and sits far below it.  2^-22 |L2| + 1e-6: the fp32 store of offset + log2(denominator) and the hardware exp2 / log2 (about 1 ulp each).  The worst
+ratio of a case is printed as `lse_ratio`.
+
     python tools/route_check.py [case-id-substring ...]      # prints one line per case, then `ROUTE_SUMMARY {json}`
 """
 import json
@@ -414,9 +431,11 @@ def run_attn(c, ops, gen):
     def launch():
         o = Guarded(1, total, BF, guard=g)
         ov = o.view.reshape(B, Nq, C)
+        ls = [Guarded(1, B * H * Nq, torch.float32, guard=g) for _ in range(2 if nk2 else 1)]
         ops.attention(dq, dk, dv, B, H, Nq, Nk, D, scale, qs, ks, vs, out=ov, rel_h=dev_rel[0], rel_w=dev_rel[1],
-                      kH=rel[0] if rel else 0, kW=rel[1] if rel else 0, seg2=seg)
-        return o, None
+                      kH=rel[0] if rel else 0, kW=rel[1] if rel else 0, seg2=seg, lse=ls[0].view.reshape(B, H, Nq),
+                      lse2=ls[1].view.reshape(B, H, Nq) if nk2 else None)
+        return o, None, ls
 
     Q4, K4, V4 = view4(q, Nq, qs), view4(k, Nk, ks), view4(v, Nk, vs)
     qsel = torch.tensor(sorted(set(range(max(0, Nq - 128), Nq)) | set(range(min(32, Nq))) |
@@ -424,6 +443,16 @@ def run_attn(c, ops, gen):
     pairs = sorted({(0, 0), (B - 1, H - 1), (int(torch.randint(0, B, (1,), generator=gen)), int(torch.randint(0, H, (1,), generator=gen))),
                     (int(torch.randint(0, B, (1,), generator=gen)), int(torch.randint(0, H, (1,), generator=gen)))})
     refs, bnds = [], []
+    lrefs, lbnds = [[], []], [[], []]     # log-sum-exp per segment (see "Bound, log-sum-exp" in the module docstring)
+    LOG2E = 1.4426950408889634
+
+    def lse_ref(S, qk_abs, bias_max=None):
+        L2 = torch.logsumexp(S, -1) * LOG2E
+        per_logit = 2.0 ** -8 + (A_ACC + 2.0 ** -9) * scale * qk_abs.max(1).values
+        if bias_max is not None:
+            per_logit = per_logit + 2.0 ** -9 * bias_max
+        return L2, LOG2E * per_logit + 2.0 ** -22 * L2.abs() + 1e-6
+
     for bb, hh in pairs:
         qq = Q4[bb, hh, qsel]
         S = (qq @ K4[bb, hh].t()) * scale
@@ -431,18 +460,25 @@ def run_attn(c, ops, gen):
             kH, kW = rel
             bh = bb * H + hh
             S = S + relh[bh, qsel].to(F64).repeat_interleave(kW, 1) + relw[bh, qsel].to(F64).repeat(1, kH)
+            bmax = (relh[bh, qsel].abs().to(F64).max(1).values + relw[bh, qsel].abs().to(F64).max(1).values)[:, None]
+        L2, lb = lse_ref(S, qq.abs() @ K4[bb, hh].abs().t(), bmax[:, 0] if rel else None)
+        lrefs[0].append(L2)
+        lbnds[0].append(lb)
         p = torch.softmax(S, -1)
         r = p @ V4[bb, hh]
         sv = p @ V4[bb, hh].abs()
         if nk2:
             K2 = k2.as_strided((B, H, nk2, D), st2 + (1,), 0).to(F64)
             V2 = k2.as_strided((B, H, nk2, D), st2 + (1,), C).to(F64)
-            p2 = torch.softmax((qq @ K2[bb, hh].t()) * scale, -1)
+            S2 = (qq @ K2[bb, hh].t()) * scale
+            L2, lb = lse_ref(S2, qq.abs() @ K2[bb, hh].abs().t())
+            lrefs[1].append(L2)
+            lbnds[1].append(lb)
+            p2 = torch.softmax(S2, -1)
             r = r + float(s2[bb]) * (p2 @ V2[bb, hh])
             sv = sv + float(s2[bb]) * (p2 @ V2[bb, hh].abs())
         bnd = 2.0 ** -8 * r.abs() + 2.0 ** -8 * sv
         if rel:   # the bias may enter the logit MFMA chain as bf16 operands (BIAS 3): each logit off by <= 2^-9 (|rel_h| + |rel_w|)
-            bmax = (relh[bh, qsel].abs().to(F64).max(1).values + relw[bh, qsel].abs().to(F64).max(1).values)[:, None]
             bnd = bnd + 2.0 ** -9 * bmax * (sv + r.abs())
         refs.append(r)
         bnds.append(bnd + 1e-30)
@@ -451,7 +487,13 @@ def run_attn(c, ops, gen):
         ov = o.view.reshape(B, Nq, H, D).cpu()
         return torch.cat([ov[bb, qsel, hh] for bb, hh in pairs])
 
-    return dict(launch=launch, ref=torch.cat(refs), bnd=torch.cat(bnds), gather=gather, cs=False, conv=False, label=None, split=None, f32=False)
+    def gather_lse(ls):
+        lv = ls.view.reshape(B, H, Nq).cpu()
+        return torch.cat([lv[bb, hh, qsel] for bb, hh in pairs])[:, None]
+
+    lse = [dict(name=n, ref=torch.cat(lrefs[i])[:, None], bnd=torch.cat(lbnds[i])[:, None]) for i, n in enumerate(("lse", "lse2")[:2 if nk2 else 1])]
+    return dict(launch=launch, ref=torch.cat(refs), bnd=torch.cat(bnds), gather=gather, cs=False, conv=False, label=None, split=None, f32=False,
+                lse=lse, gather_lse=gather_lse)
 
 
 # --------------------------------------------------------------------------------------------------- mirrors
@@ -486,23 +528,33 @@ def run_case(c, ops):
     op = c["op"]
     spec = (run_conv(c, ops, gen) if op == "conv" else run_up2(c, ops, gen) if op == "up2" else run_gemm(c, ops, gen, ln=(op == "ln"))
             if op in ("gemm", "ln") else run_attn(c, ops, gen))
-    (o1, st1), names = profiled(spec["launch"])
+    (o1, st1, *ex1), names = profiled(spec["launch"])
+    ex1 = ex1[0] if ex1 else []          # attention: the guarded log-sum-exp buffers
     names, keys = route_keys(names)
     res = dict(id=c["id"], kernels=names, keys=sorted(set(keys)), ok=False, ratio=None, guards=None, mirror=None, error=None)
+    if "lse" in spec:
+        res["lse_ratio"] = None
     try:
         want = RC.expected_kernels(c["id"])
         missing = [k for k in want if k not in keys]
         if missing:
             raise CaseFailure(f"declared instantiation(s) not reached: {missing}")
         res["mirror"] = mirror_check(spec, keys)
-        o2, st2 = spec["launch"]()
+        o2, st2, *ex2 = spec["launch"]()
+        ex2 = ex2[0] if ex2 else []
         torch.cuda.synchronize()
-        gd = o1.guards_intact() and o2.guards_intact() and all(s.guards_intact() for s in (st1, st2) if s is not None)
+        gd = o1.guards_intact() and o2.guards_intact() and all(s.guards_intact() for s in [st1, st2] + ex1 + ex2 if s is not None)
         res["guards"] = "intact" if gd else "CLOBBERED"
         if not gd:
             raise CaseFailure("a guard area was written")
         if not torch.equal(o1.bits(), o2.bits()) or (st1 is not None and not torch.equal(st1.bits(), st2.bits())):
             raise CaseFailure("two runs differ")
+        for info, a, b in zip(spec.get("lse", []), ex1, ex2):
+            if not torch.equal(a.bits(), b.bits()):
+                raise CaseFailure(f"{info['name']}: two runs differ")
+            unwritten = int((a.bits() == a.sent).sum())
+            if unwritten:
+                raise CaseFailure(f"{info['name']}: {unwritten} of {a.cols} (batch, head, query) entries were never written")
         if "gather" in spec:
             got = spec["gather"](o1)
         else:
@@ -521,6 +573,11 @@ def run_case(c, ops):
                 ratio = max(ratio, stats_check(st1.view.cpu(), y, 64, "row statistics", per_row=True))
             else:
                 ratio = max(ratio, stats_check(st1.view.cpu(), y, 32, "column statistics", sample_rows=spec.get("sample_rows", 0)))
+        if "lse" in spec:
+            got_l = [spec["gather_lse"](a) for a in ex1]
+            res["lse_ratio"] = max(float(((g.to(F64) - info["ref"]).abs() / info["bnd"]).nan_to_num(float("inf")).max()) for info, g in zip(spec["lse"], got_l))
+            for info, g in zip(spec["lse"], got_l):
+                bound_check(g, info["ref"], info["bnd"], info["name"])
         res["ratio"], res["ok"] = ratio, True
     except CaseFailure as e:
         res["error"] = str(e)
@@ -548,6 +605,8 @@ def main():
             break
         results.append(r)
         rt = f"{r['ratio']:.3f}" if r["ratio"] is not None else "-"
+        if "lse_ratio" in r:
+            rt += " lse_ratio " + (f"{r['lse_ratio']:.3f}" if r["lse_ratio"] is not None else "-")
         print(f"{'PASS' if r['ok'] else 'FAIL'} {r['id']:24s} {time.time() - t1:5.1f}s ratio {rt:>6s} guards {r['guards']} mirror {r['mirror']} "
               f"kernels {r['keys'] or r['kernels']}" + (f"  ERROR {r['error']}" if r["error"] else ""), flush=True)
     summary = dict(results=results, aborted=aborted, seconds=round(time.time() - t0, 1))
