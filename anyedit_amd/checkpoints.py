@@ -256,6 +256,29 @@ def load_dinov2(module, path_or_state_dict, location="cpu"):
     return "dinov2"
 
 
+def load_groundingdino_backbone(model, path_or_state_dict, location="cpu"):
+    """Fills a `groundingdino.swin_transformer.SwinTransformer` from a file or a state dict.  Recognised forms: a bare Swin state dict
+    (`patch_embed.*`, `layers.I.*`, `normI.*`); a GroundingDINO checkpoint (groundingdino/util/inference.py:35-36 `torch.load(path)["model"]`)
+    whose backbone sits under `backbone.0.` (`Joiner[0]`; every other entry is ignored); the same with a `module.` prefix in front.  The
+    persistent `relative_position_index` buffers are checked against the computed ones.  Missing or unexpected keys are reported as
+    `load_state_dict(strict=True)` reports them.  Returns the form found."""
+    sd = path_or_state_dict
+    if not isinstance(sd, dict):
+        from anyedit_amd.cldm.model import load_state_dict
+        sd = load_state_dict(sd, location)
+    layout = "swin"
+    if isinstance(sd.get("model"), dict):
+        sd = sd["model"]
+        layout = "groundingdino"
+    for prefix, name in (("module.backbone.0.", "groundingdino-module"), ("backbone.0.", "groundingdino")):
+        if any(k.startswith(prefix) for k in sd):
+            sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+            layout = name
+            break
+    model.load_state_dict(sd, strict=True)
+    return layout
+
+
 def load_sd_checkpoint(path, unet=None, vae=None, text_encoder=None, location="cpu"):
     """`load_unet_weights`' sibling for a FULL SD-1.5 state dict (CompVis lineage): routes `model.diffusion_model.*` to `unet`,
     `first_stage_model.*` to `vae` and `cond_stage_model.*` to `text_encoder` (a FrozenCLIPEmbedder); a part given as None is skipped.

@@ -1052,6 +1052,84 @@ def swiglu(u, bias, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- GroundingDINO's Swin backbone (csrc/swin.hip)
+SWIN_HEAD_DIM = 32
+SWIN_MAX_WINDOW = 16
+SWIN_MERGE_CMAX = 1024
+
+
+def swin_window_attention(qkv, qkv_bias, bias, B, H, W, heads, window, shift, scale, out=None):
+    """Shifted-window attention of one Swin block on rows in IMAGE order: qkv bf16 [B*H*W, 3C] (unit inner stride, row stride free: the packed
+    q | k | v of `gemm(norm1(x), Wqkv, bqkv)`), qkv_bias fp32 [3C] (what a pad token's key and value are), bias fp32 [heads, N, N] contiguous
+    (N = window^2: the gathered relative position bias) -> out bf16 [B*H*W, C].  Pad, cyclic shift, window partition, the -100 shift mask, window
+    reverse, shift back and crop are the kernel's row addressing.  head_dim C / heads must be 32, window <= 16, 0 <= shift < window."""
+    _chk(qkv, BF16, "swin_window_attention.qkv", 2)
+    _chk(qkv_bias, torch.float32, "swin_window_attention.qkv_bias", 1)
+    _chk(bias, torch.float32, "swin_window_attention.bias", 3)
+    M, C3 = qkv.shape
+    if C3 % 3 or qkv.stride(1) != 1:
+        raise ValueError(f"swin_window_attention: qkv must be [rows, 3C] with unit inner stride, got {tuple(qkv.shape)}")
+    C = C3 // 3
+    if heads <= 0 or C % heads or C // heads != SWIN_HEAD_DIM:
+        raise ValueError(f"swin_window_attention: head_dim {C}/{heads} must be {SWIN_HEAD_DIM} (the only one ae_swin_window_attn_bf16 is built for)")
+    if not 1 <= window <= SWIN_MAX_WINDOW:
+        raise ValueError(f"swin_window_attention: window size {window} must be in [1, {SWIN_MAX_WINDOW}]")
+    if not 0 <= shift < window:
+        raise ValueError(f"swin_window_attention: shift {shift} must be in [0, window size {window})")
+    if B <= 0 or H <= 0 or W <= 0 or M != B * H * W:
+        raise ValueError(f"swin_window_attention: {M} rows are not B*H*W = {B}*{H}*{W}")
+    N = window * window
+    if tuple(bias.shape) != (heads, N, N) or not bias.is_contiguous():
+        raise ValueError(f"swin_window_attention: bias must be a contiguous [{heads}, {N}, {N}] tensor, got {tuple(bias.shape)}")
+    if qkv_bias.numel() != C3 or not qkv_bias.is_contiguous():
+        raise ValueError(f"swin_window_attention: qkv_bias must hold {C3} values")
+    if out is None:
+        out = torch.empty(M, C, dtype=BF16, device=qkv.device)
+    _chk(out, BF16, "swin_window_attention.out", 2)
+    if tuple(out.shape) != (M, C) or out.stride(1) != 1:
+        raise ValueError(f"swin_window_attention: out must be [{M}, {C}] with unit inner stride")
+    check(lib.ae_swin_window_attn_bf16(_p(qkv), qkv.stride(0), _p(qkv_bias), _p(bias), _p(out), out.stride(0), B, H, W, C, heads, window, shift, float(scale),
+                                       _s()), "ae_swin_window_attn_bf16")
+    return out
+
+
+def swin_merge_layernorm(x, gamma, beta, B, H, W, eps=1e-5, out=None):
+    """PatchMerging up to its norm: x bf16 [B*H*W, C] contiguous (rows of an H x W map) -> LayerNorm over 4C of cat(x(2i, 2j), x(2i+1, 2j),
+    x(2i, 2j+1), x(2i+1, 2j+1)) as bf16 [B*ceil(H/2)*ceil(W/2), 4C]; positions outside an odd map are zeros that enter the statistics.
+    gamma / beta fp32 [4C].  C % 8 == 0, C <= 1024."""
+    _chk(x, BF16, "swin_merge_layernorm.x", 2)
+    _chk(gamma, torch.float32, "swin_merge_layernorm.gamma", 1)
+    _chk(beta, torch.float32, "swin_merge_layernorm.beta", 1)
+    M, C = x.shape
+    if B <= 0 or H <= 0 or W <= 0 or M != B * H * W or not x.is_contiguous():
+        raise ValueError(f"swin_merge_layernorm: x must be a contiguous [B*H*W, C] = [{B}*{H}*{W}, C] buffer, got {tuple(x.shape)}")
+    if C % 8 or C > SWIN_MERGE_CMAX:
+        raise ValueError(f"swin_merge_layernorm: width {C} must be a multiple of 8 and at most {SWIN_MERGE_CMAX}")
+    if gamma.numel() != 4 * C or beta.numel() != 4 * C or not gamma.is_contiguous() or not beta.is_contiguous():
+        raise ValueError(f"swin_merge_layernorm: gamma and beta must hold 4C = {4 * C} values")
+    M2 = B * ((H + 1) // 2) * ((W + 1) // 2)
+    if out is None:
+        out = torch.empty(M2, 4 * C, dtype=BF16, device=x.device)
+    _chk(out, BF16, "swin_merge_layernorm.out", 2)
+    if tuple(out.shape) != (M2, 4 * C) or not out.is_contiguous():
+        raise ValueError(f"swin_merge_layernorm: out must be a contiguous [{M2}, {4 * C}] buffer")
+    check(lib.ae_swin_merge_ln_bf16(_p(x), _p(gamma), _p(beta), _p(out), B, H, W, C, float(eps), _s()), "ae_swin_merge_ln_bf16")
+    return out
+
+
+def rows_to_nchw_out(x, out):
+    """channels-last bf16 rows [B*H*W, C] contiguous -> the given [B, C, H, W] buffer (fp32 or bf16, contiguous): `rows_to_nchw` into a
+    buffer the caller owns (no allocation)."""
+    _chk(x, BF16, "rows_to_nchw_out.x", 2)
+    if not out.is_cuda or out.dtype not in (torch.float32, BF16) or out.dim() != 4 or not out.is_contiguous():
+        raise ValueError("rows_to_nchw_out: out must be a contiguous fp32 / bf16 [B, C, H, W] GPU tensor")
+    B, C, H, W = out.shape
+    if tuple(x.shape) != (B * H * W, C) or not x.is_contiguous():
+        raise ValueError(f"rows_to_nchw_out: x must be a contiguous [{B * H * W}, {C}] buffer, got {tuple(x.shape)}")
+    check(lib.ae_transpose_last2(_p(x), _p(out), B, H * W, C, H * W, 1, 1 if out.dtype == BF16 else 0, _s()), "ae_transpose_last2")
+    return out
+
+
 # --------------------------------------------------------------------------- layout / elementwise
 def nchw_to_rows(x, c_pad=None):
     """[B,C,H,W] (fp32 or bf16) -> channels-last bf16 [B*H*W, Cpad] (zero padded channels)."""

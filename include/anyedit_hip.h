@@ -478,6 +478,32 @@ int ae_dino_embed_bf16(const float* patch, long ldp, const float* patch_bias, co
                        int C, void* stream);
 int ae_swiglu_f32_bf16(const float* u, long ldu, const float* bias, void* y, long ldy, long M, int Hd, void* stream);
 
+/* ---- GroundingDINO's Swin backbone (GroundingDINO/groundingdino/models/GroundingDINO/backbone/swin_transformer.py:501-759 SwinTransformer,
+ * built by build_swin_transformer :762-791; the detector of tools/tool.py runs it on every image).  Patch embedding is ae_clip_patch_rows_bf16 with
+ * P = 4 + ae_gemm_bf16 + ae_layernorm_bf16, every norm ae_layernorm_bf16, qkv / proj / fc2 ae_gemm_bf16 (residual adds in the epilogue), fc1's GELU
+ * ae_bias_act_f32_bf16, the NCHW outputs ae_transpose_last2; these two are the rest.  Both write bf16 with one rounding at the store, use no
+ * scratch and no atomics.
+ * ae_swin_window_attn_bf16: SwinTransformerBlock.forward from the pad after norm1 to the crop (:253-292) around the core of WindowAttention.forward
+ *   (:140-171).  qkv: bf16 rows in IMAGE order [B*H*W, 3C] with row stride ldq, the packed output of one ae_gemm_bf16 (+bias) on norm1(x): column
+ *   s*C + head*32 + j holds (q, k, v)[s] of that head (reshape(B_, N, 3, nH, D)).  out: bf16 rows in image order [B*H*W, C], row stride ldo.
+ *   With Hp, Wp = H, W rounded up to multiples of ws, the token at in-window position (i, j) of window (wy, wx) has the shifted-frame coordinate
+ *   (ys, xs) = (wy*ws + i, wx*ws + j) and the image coordinate ((ys + shift) mod Hp, (xs + shift) mod Wp); it is read from and written to that
+ *   image row — no padded, rolled or partitioned copy exists.  A token with y >= H or x >= W is a pad token: its key and value are qkv_bias
+ *   rounded to bf16 (the reference pads norm1's output with zeros, then applies qkv), it takes part in the softmax as a key, and its output row is
+ *   never written.  Logits scale * q k^T + bias[head][query][key] are fp32 (bias: fp32 [nH, N, N], N = ws*ws, relative_position_bias_table
+ *   gathered through relative_position_index); for shift > 0 exactly -100.0 is added where the regions 3 r(ys) + r(xs) of query and key differ,
+ *   r(p) = 0 for p < L - ws, 1 for p < L - shift, 2 otherwise, L = Hp resp. Wp (BasicLayer.forward :417-443, computed in the kernel).  fp32
+ *   softmax; probabilities are rounded to bf16 only as MFMA operands of P V.  head_dim C / nH must be 32, 1 <= ws <= 16, 0 <= shift < ws,
+ *   ldq >= 3C, ldo >= C, both multiples of 8, pointers 16-byte aligned, B*H*W < 2^31; anything else is refused.  One launch covers all samples,
+ *   windows and heads.
+ * ae_swin_merge_ln_bf16: PatchMerging.forward up to the norm (:320-337): x bf16 [B, H, W, C] contiguous -> y bf16 [B*ceil(H/2)*ceil(W/2), 4C],
+ *   row (b, i, j) = LayerNorm over 4C of cat(x(2i, 2j), x(2i+1, 2j), x(2i, 2j+1), x(2i+1, 2j+1)); a position outside the map is zeros and those
+ *   zeros enter the statistics (the reference pads, then normalises).  gamma / beta fp32 [4C].  C % 8 == 0, 4C <= 4096, pointers 16-byte aligned.
+ *   The `reduction` Linear behind it is an ae_gemm_bf16 without bias.                                                                          */
+int ae_swin_window_attn_bf16(const void* qkv, long ldq, const float* qkv_bias, const float* bias, void* out, long ldo, int B, int H, int W, int C,
+                             int nH, int ws, int shift, float scale, void* stream);
+int ae_swin_merge_ln_bf16(const void* x, const float* gamma, const float* beta, void* y, int B, int H, int W, int C, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
