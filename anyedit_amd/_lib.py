@@ -131,10 +131,15 @@ SIGNATURES = {
     "ae_swiglu_f32_bf16": [c_void_p, c_long, c_void_p, c_void_p, c_long, c_long, c_int, c_void_p],
     "ae_swin_window_attn_bf16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p],
     "ae_swin_merge_ln_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p],
+    "ae_scale_residual_f32_bf16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_long, c_int, c_void_p],
+    "ae_biattn_split_rows": [c_int],
+    "ae_biattn_workspace_bytes": [c_int, c_int, c_int, c_int, c_int],
+    "ae_biattn_bf16": [c_void_p, c_long] * 4 + [c_void_p, c_void_p] + [c_void_p, c_long] * 2 + [c_int] * 5 + [c_float, c_void_p, c_long, c_void_p],
+    "ae_attn_masked_short_bf16": [c_void_p] * 5 + [c_int] * 4 + [c_long] * 12 + [c_float, c_void_p],
 }
 _RESTYPES = {"ae_last_error": ctypes.c_char_p, "ae_groupnorm_workspace_floats": c_long, "ae_conv3x3_workspace_floats": c_long,
              "ae_groupnorm_bwd_workspace_floats": c_long, "ae_attn_fp8_workspace_bytes": c_long, "ae_attn_bwd_workspace_floats": c_long,
-             "ae_xattn_fused_kv_bytes": c_long}
+             "ae_xattn_fused_kv_bytes": c_long, "ae_biattn_workspace_bytes": c_long}
 
 
 class AnyEditHipError(RuntimeError):

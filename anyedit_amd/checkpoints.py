@@ -279,6 +279,34 @@ def load_groundingdino_backbone(model, path_or_state_dict, location="cpu"):
     return layout
 
 
+def load_groundingdino_encoder(module, path_or_state_dict, location="cpu"):
+    """Fills a `groundingdino.transformer.TransformerEncoder` (the feature enhancer) from a file or a state dict.  Recognised forms: a bare
+    encoder state dict (`layers.I.*`, `text_layers.I.*`, `fusion_layers.I.*`); a GroundingDINO checkpoint (`torch.load(path)["model"]` or the
+    dict itself) whose enhancer sits under `transformer.encoder.` (every other entry is ignored); the same with a `module.` prefix in front.
+    Strict: a key the module has and the checkpoint lacks, or the reverse, raises a KeyError that names it.  Returns the form found."""
+    sd = path_or_state_dict
+    if not isinstance(sd, dict):
+        from anyedit_amd.cldm.model import load_state_dict
+        sd = load_state_dict(sd, location)
+    layout = "encoder"
+    if isinstance(sd.get("model"), dict):
+        sd = sd["model"]
+    for prefix, name in (("module.transformer.encoder.", "groundingdino-module"), ("transformer.encoder.", "groundingdino")):
+        if any(k.startswith(prefix) for k in sd):
+            sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+            layout = name
+            break
+    own = module.state_dict()
+    missing = sorted(k for k in own if k not in sd)
+    if missing:
+        raise KeyError(f"load_groundingdino_encoder: {len(missing)} tensor(s) of the module are not in the checkpoint ({layout} form), first: '{missing[0]}'")
+    unexpected = sorted(k for k in sd if k not in own)
+    if unexpected:
+        raise KeyError(f"load_groundingdino_encoder: {len(unexpected)} checkpoint tensor(s) have no place in the module ({layout} form), first: '{unexpected[0]}'")
+    module.load_state_dict(sd, strict=True)
+    return layout
+
+
 def load_sd_checkpoint(path, unet=None, vae=None, text_encoder=None, location="cpu"):
     """`load_unet_weights`' sibling for a FULL SD-1.5 state dict (CompVis lineage): routes `model.diffusion_model.*` to `unet`,
     `first_stage_model.*` to `vae` and `cond_stage_model.*` to `text_encoder` (a FrozenCLIPEmbedder); a part given as None is skipped.

@@ -1117,6 +1117,122 @@ def swin_merge_layernorm(x, gamma, beta, B, H, W, eps=1e-5, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- GroundingDINO's feature enhancer (csrc/gdino_encoder.hip)
+BIATTN_HEAD_DIM = 256
+BIATTN_MAX_TEXT = 256
+MASKED_SHORT_MAX_N = 256
+_BIATTN_WS = {}
+
+
+def bi_attention_split_rows(Nv):
+    """Image tokens per partial of the text direction of `bi_attention` (ae_biattn_split_rows): it is merged from ceil(Nv / rows) partials."""
+    return lib.ae_biattn_split_rows(int(Nv))
+
+
+def _rows3(t, name, B, N, C):
+    _chk(t, BF16, name, 3)
+    if tuple(t.shape) != (B, N, C) or t.stride(2) != 1 or (B > 1 and t.stride(0) != N * t.stride(1)):
+        raise ValueError(f"{name}: expected [{B}, {N}, {C}] rows with unit inner stride and one row stride over all samples, got shape {tuple(t.shape)} "
+                         f"strides {tuple(t.stride())}")
+    return t.stride(1)
+
+
+def bi_attention(q, k, val_v, val_l, heads, scale, mask_v=None, mask_l=None, out_v=None, out_l=None):
+    """The two attentions of BiMultiHeadAttention (fuse_modules.py:174-225) over ONE logit matrix scale q k^T, head_dim 256:
+        out_v [B, Nv, heads*256] = softmax over text keys (mask_l removed) of the logits, times val_l
+        out_l [B, Nt, heads*256] = softmax over image keys (mask_v removed) of the transposed logits, times val_v
+    q / val_v: bf16 [B, Nv, heads*256], k / val_l: bf16 [B, Nt, heads*256] (unit inner stride, any row stride).  mask_v [B, Nv] / mask_l [B, Nt]:
+    bool or uint8, True = a PADDED token (the reference's sense), removed as a key; rows of padded queries are computed like any others.
+    CONTRACT, not checked (it would be a host synchronisation): every sample has at least one unmasked text token and one unmasked image token.
+    The global-maximum subtraction and the +-50000 clamps of the reference are left out (include/anyedit_hip.h).  Nt in [1, 256], Nv >= 1.  No
+    buffer of size ~ Nv*Nt exists; the workspace (ae_biattn_workspace_bytes) is grow-only per (device, stream), so a warmed-up call allocates
+    nothing besides outputs the caller did not pass."""
+    _chk(q, BF16, "bi_attention.q", 3)
+    _chk(k, BF16, "bi_attention.k", 3)
+    B, Nv, C = q.shape
+    Nt = k.shape[1]
+    if heads <= 0 or C % heads or C // heads != BIATTN_HEAD_DIM:
+        raise ValueError(f"bi_attention: head_dim {C}/{heads} must be {BIATTN_HEAD_DIM} (the only one ae_biattn_bf16 is built for)")
+    if not 1 <= Nt <= BIATTN_MAX_TEXT:
+        raise ValueError(f"bi_attention: {Nt} text tokens; ae_biattn_bf16 takes between 1 and {BIATTN_MAX_TEXT}")
+    if Nv < 1:
+        raise ValueError("bi_attention: no image tokens")
+    ldq, ldk = _rows3(q, "bi_attention.q", B, Nv, C), _rows3(k, "bi_attention.k", B, Nt, C)
+    ldvv, ldvl = _rows3(val_v, "bi_attention.val_v", B, Nv, C), _rows3(val_l, "bi_attention.val_l", B, Nt, C)
+    if out_v is None:
+        out_v = torch.empty(B, Nv, C, dtype=BF16, device=q.device)
+    if out_l is None:
+        out_l = torch.empty(B, Nt, C, dtype=BF16, device=q.device)
+    ldov, ldol = _rows3(out_v, "bi_attention.out_v", B, Nv, C), _rows3(out_l, "bi_attention.out_l", B, Nt, C)
+    masks = []
+    for m, n, name in ((mask_v, Nv, "mask_v"), (mask_l, Nt, "mask_l")):
+        if m is not None:
+            if m.dtype == torch.bool:
+                m = m.view(torch.uint8)
+            _chk(m, torch.uint8, "bi_attention." + name, 2)
+            if tuple(m.shape) != (B, n) or not m.is_contiguous():
+                raise ValueError(f"bi_attention: {name} must be a contiguous [{B}, {n}] bool / uint8 tensor, got {tuple(m.shape)}")
+        masks.append(m)
+    need = lib.ae_biattn_workspace_bytes(B, heads, Nv, Nt, BIATTN_HEAD_DIM)
+    if need <= 0:
+        raise ValueError(f"bi_attention: unsupported sizes B={B} heads={heads} Nv={Nv} Nt={Nt}")
+    key = (q.device, torch.cuda.current_stream(q.device).cuda_stream)
+    ws = _BIATTN_WS.get(key)
+    if ws is None or ws.numel() < need:  # grow-only scratch per (device, stream): the call owns it until the next call on that stream
+        ws = _BIATTN_WS[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
+    check(lib.ae_biattn_bf16(_p(q), ldq, _p(k), ldk, _p(val_v), ldvv, _p(val_l), ldvl, _p(masks[0]), _p(masks[1]), _p(out_v), ldov, _p(out_l), ldol,
+                             B, heads, Nv, Nt, BIATTN_HEAD_DIM, float(scale), _p(ws), ws.numel(), _s()), "ae_biattn_bf16")
+    return out_v, out_l
+
+
+def scale_residual(u, res, gamma=None, bias=None, out=None):
+    """out = res + gamma * (u + bias) as bf16, one rounding: u fp32 [M, N] (unit inner stride), res bf16 [M, N], gamma / bias fp32 [N] or None
+    (1 / 0).  BiAttentionBlock's layer-scaled residual and the residual behind the fp32 deformable attention."""
+    _chk(u, torch.float32, "scale_residual.u", 2)
+    _chk(res, BF16, "scale_residual.res", 2)
+    M, N = u.shape
+    if tuple(res.shape) != (M, N) or u.stride(1) != 1 or res.stride(1) != 1:
+        raise ValueError(f"scale_residual: u and res must both be [{M}, {N}] with unit inner stride")
+    for t, n in ((gamma, "gamma"), (bias, "bias")):
+        if t is not None:
+            _chk(t, torch.float32, "scale_residual." + n, 1)
+            if t.numel() != N or not t.is_contiguous():
+                raise ValueError(f"scale_residual: {n} must hold {N} values")
+    if out is None:
+        out = torch.empty(M, N, dtype=BF16, device=u.device)
+    _chk(out, BF16, "scale_residual.out", 2)
+    if tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise ValueError(f"scale_residual: out must be [{M}, {N}] with unit inner stride")
+    check(lib.ae_scale_residual_f32_bf16(_p(u), u.stride(0), _p(bias), _p(gamma), _p(res), res.stride(0), _p(out), out.stride(0), M, N, _s()),
+          "ae_scale_residual_f32_bf16")
+    return out
+
+
+def attention_masked_short(q, k, v, mask, B, H, N, D, scale, q_strides, k_strides, v_strides, out=None):
+    """Self-attention over at most 256 tokens with a full boolean mask (GroundingDINO's text layers): q/k/v bf16 tensors addressed through
+    (batch, head, row) element strides as in `attention_causal_short`; mask uint8 (or bool) [B*H, N, N] contiguous, slice b*H + h, True = the key
+    is ALLOWED for that query row; out [B, N, H*D] bf16.  CONTRACT: every row allows at least one key.  N in [1, 256], D in {32, 64}."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _chk(t, BF16, "attention_masked_short." + n)
+    if not 1 <= N <= MASKED_SHORT_MAX_N:
+        raise ValueError(f"attention_masked_short: sequence length {N}; ae_attn_masked_short_bf16 takes between 1 and {MASKED_SHORT_MAX_N}")
+    if D not in (32, 64):
+        raise ValueError(f"attention_masked_short: head_dim {D} is not built (supported: 32, 64)")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    _chk(mask, torch.uint8, "attention_masked_short.mask", 3)
+    if tuple(mask.shape) != (B * H, N, N) or not mask.is_contiguous():
+        raise ValueError(f"attention_masked_short: mask must be a contiguous [{B * H}, {N}, {N}] tensor, got {tuple(mask.shape)}")
+    if out is None:
+        out = torch.empty(B, N, H * D, dtype=BF16, device=q.device)
+    _chk(out, BF16, "attention_masked_short.out")
+    if out.numel() != B * N * H * D or not out.is_contiguous():
+        raise ValueError(f"attention_masked_short: out must be a contiguous [{B}, {N}, {H * D}] buffer")
+    check(lib.ae_attn_masked_short_bf16(_p(q), _p(k), _p(v), _p(mask), _p(out), B, H, N, D, *q_strides, *k_strides, *v_strides, N * H * D, D, H * D,
+                                        float(scale), _s()), "ae_attn_masked_short_bf16")
+    return out
+
+
 def rows_to_nchw_out(x, out):
     """channels-last bf16 rows [B*H*W, C] contiguous -> the given [B, C, H, W] buffer (fp32 or bf16, contiguous): `rows_to_nchw` into a
     buffer the caller owns (no allocation)."""
@@ -1408,10 +1524,12 @@ def gaussian_moments(moments, noise=None, want_stats=False):
     return (z, *stats) if want_stats else z
 
 
-def ms_deform_attn(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step=None):
+def ms_deform_attn(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step=None, validated=False):
     """Drop-in for `_C.ms_deform_attn_forward` (GroundingDINO ms_deform_attn.py:42-60): value [bs, S, heads, d], spatial_shapes
     [L, 2] int64, level_start_index [L] int64, sampling_locations [bs, Q, heads, L, P, 2], attention_weights [bs, Q, heads, L, P]
-    -> [bs, Q, heads*d] fp32.  `im2col_step` is accepted for signature compatibility (it only chunked the CUDA launch)."""
+    -> [bs, Q, heads*d] fp32.  `im2col_step` is accepted for signature compatibility (it only chunked the CUDA launch).
+    `validated=True`: the caller has checked on the host that the levels add up to S (the check here reads the device tensor back, a
+    synchronisation no graph capture allows)."""
     _chk(value, torch.float32, "ms_deform_attn.value", 4)
     bs, S, heads, d = value.shape
     _, Q, _, L, P, _ = sampling_locations.shape
@@ -1420,7 +1538,7 @@ def ms_deform_attn(value, spatial_shapes, level_start_index, sampling_locations,
     w = attention_weights.float().contiguous()
     shapes = spatial_shapes.to(torch.int64).contiguous()
     starts = level_start_index.to(torch.int64).contiguous()
-    if int(shapes.prod(1).sum()) != S:
+    if not validated and int(shapes.prod(1).sum()) != S:
         raise ValueError("ms_deform_attn: spatial_shapes do not add up to value.shape[1]")
     out = torch.empty(bs, Q, heads * d, dtype=torch.float32, device=value.device)
     check(lib.ae_ms_deform_attn_fwd_f32(_p(value), _p(shapes), _p(starts), _p(loc), _p(w), _p(out), bs, S, heads, d, Q, L, P, _s()),

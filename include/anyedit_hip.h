@@ -504,6 +504,45 @@ int ae_swin_window_attn_bf16(const void* qkv, long ldq, const float* qkv_bias, c
                              int nH, int ws, int shift, float scale, void* stream);
 int ae_swin_merge_ln_bf16(const void* x, const float* gamma, const float* beta, void* y, int B, int H, int W, int C, float eps, void* stream);
 
+/* ---- GroundingDINO's feature enhancer (GroundingDINO/groundingdino/models/GroundingDINO/transformer.py:406-595 TransformerEncoder: per layer a
+ * BiAttentionBlock (fuse_modules.py:252-295), a text TransformerEncoderLayer (transformer_vanilla.py:72-123) and a
+ * DeformableTransformerEncoderLayer (transformer.py:738-799)).  LayerNorms are ae_layernorm_bf16, projections and feed-forwards ae_gemm_bf16 /
+ * ae_ln_gemm_bf16 (EPI_RELU), the deformable attention ae_linear_f32 + ae_ms_deform_attn_fwd_f32; these are the rest (csrc/gdino_encoder.hip).
+ * No atomics, no scratch; every launch is deterministic.
+ * ae_biattn_bf16: BiMultiHeadAttention.forward between the projections (fuse_modules.py:174-225), head_dim D = 256 only.  All rows bf16, row r of
+ *   sample b at (b*N + r) * ld, head h in columns [h*D, (h+1)*D):  q [B, Nv] = v_proj output (the scale of :162 is passed as `scale` and applied to
+ *   the fp32 logits), k [B, Nt] = l_proj output, val_v [B, Nv], val_l [B, Nt].  mask_v [B, Nv] / mask_l [B, Nt]: uint8, may be null; NON-ZERO = a
+ *   PADDED token (the reference's sense, True = padding: :205-218 masked_fill(-inf)), removed as a KEY of the other stream's softmax.  Rows of
+ *   padded QUERIES are computed like any others, as the reference does.
+ *     out_v[b, i, h] = sum_j softmax_j(scale q_i . k_j over j with mask_l[b, j] == 0) val_l[j]        (:218-224)
+ *     out_l[b, j, h] = sum_i softmax_i(scale q_i . k_j over i with mask_v[b, i] == 0) val_v[i]        (:193-211, :225)
+ *   Both softmaxes are fp32 and subtract their own running maximum; probabilities are rounded to bf16 only as MFMA operands.  Left out: the
+ *   subtraction of the global attn_weights.max() (:181-182) and the clamps to +-50000 (:184-202) — a softmax is invariant to a shift of its row, so
+ *   they change a result only when the logits of one call span more than 50000.  Contract (not checked: it would be a host sync): every sample has
+ *   at least one unmasked text token and one unmasked image token.  No buffer of size ~ Nv*Nt exists: the logits are recomputed per direction.  The
+ *   text direction cuts the image tokens into partials of ae_biattn_split_rows(Nv) rows (at most 32 partials), each leaving (running maximum, sum,
+ *   fp32 accumulator) in `workspace`; a combine kernel merges them in partial order, so two launches give bit-identical outputs.  workspace:
+ *   ae_biattn_workspace_bytes(B, heads, Nv, Nt, D) bytes, 16-byte aligned, owned by the call until the next call on that stream (0 = unsupported
+ *   sizes).  1 <= Nt <= 256, Nv >= 1, B*heads <= 65535, row strides >= heads*D and multiples of 8, pointers 16-byte aligned.  Three launches.
+ * ae_attn_masked_short_bf16: the attention core of nn.MultiheadAttention as transformer_vanilla.py:115 calls it (attn_mask, no key_padding_mask):
+ *   q/k/v bf16 addressed by (batch, head, row) element strides as ae_attn_causal_short_bf16; mask uint8 [B*H, N, N] contiguous, slice b*H + h, row =
+ *   query, NON-ZERO = the key is ALLOWED (the reference passes ~text_self_attention_masks as a disallow mask, transformer.py:569; this takes the
+ *   un-negated one); out bf16 through (batch, head, row) strides.  Contract: every row allows at least one key (the reference's masks contain the
+ *   diagonal).  1 <= N <= 256, D in {32, 64}, B*H <= 65535; fp32 one-pass softmax.
+ * ae_scale_residual_f32_bf16: out = res + gamma * (u + bias), rounded to bf16 once — BiAttentionBlock's layer-scaled residual (fuse_modules.py:293-294,
+ *   u the fp32 product of out_v_proj / out_l_proj without bias) and the residual behind the fp32 deformable attention (transformer.py:793).  u fp32
+ *   [M, N] row stride ldu, bias / gamma fp32 [N] or null (0 / 1), res and out bf16.  N % 4 == 0, strides multiples of 4.                           */
+int ae_scale_residual_f32_bf16(const float* u, long ldu, const float* bias, const float* gamma, const void* res, long ldr, void* out, long ldo, long M,
+                               int N, void* stream);
+int ae_biattn_split_rows(int Nv);
+long ae_biattn_workspace_bytes(int B, int heads, int Nv, int Nt, int D);
+int ae_biattn_bf16(const void* q, long ldq, const void* k, long ldk, const void* val_v, long ldvv, const void* val_l, long ldvl, const void* mask_v,
+                   const void* mask_l, void* out_v, long ldov, void* out_l, long ldol, int B, int heads, int Nv, int Nt, int D, float scale,
+                   void* workspace, long workspace_bytes, void* stream);
+int ae_attn_masked_short_bf16(const void* q, const void* k, const void* v, const void* mask, void* out, int B, int H, int N, int D, long q_sb, long q_sh,
+                              long q_sn, long k_sb, long k_sh, long k_sn, long v_sb, long v_sh, long v_sn, long o_sb, long o_sh, long o_sn, float scale,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
