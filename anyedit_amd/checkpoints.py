@@ -307,6 +307,34 @@ def load_groundingdino_encoder(module, path_or_state_dict, location="cpu"):
     return layout
 
 
+def load_groundingdino_transformer(module, path_or_state_dict, location="cpu"):
+    """Fills a `groundingdino.transformer.Transformer` (with its heads attached: enc_out_bbox_embed, decoder.bbox_embed, ...) from a file or a
+    state dict.  Recognised forms: a bare Transformer state dict; a GroundingDINO checkpoint (`torch.load(path)["model"]` or the dict itself) whose
+    `transformer.*` entries are read — such a checkpoint lists the shared box head under `bbox_embed.*` too; only the `transformer.` copies are
+    read; the same with a `module.` prefix in front.  Strict, as `load_groundingdino_encoder`.  Returns the form found."""
+    sd = path_or_state_dict
+    if not isinstance(sd, dict):
+        from anyedit_amd.cldm.model import load_state_dict
+        sd = load_state_dict(sd, location)
+    layout = "transformer"
+    if isinstance(sd.get("model"), dict):
+        sd = sd["model"]
+    for prefix, name in (("module.transformer.", "groundingdino-module"), ("transformer.", "groundingdino")):
+        if any(k.startswith(prefix) for k in sd):
+            sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+            layout = name
+            break
+    own = module.state_dict()
+    missing = sorted(k for k in own if k not in sd)
+    if missing:
+        raise KeyError(f"load_groundingdino_transformer: {len(missing)} tensor(s) of the module are not in the checkpoint ({layout} form), first: '{missing[0]}'")
+    unexpected = sorted(k for k in sd if k not in own)
+    if unexpected:
+        raise KeyError(f"load_groundingdino_transformer: {len(unexpected)} checkpoint tensor(s) have no place in the module ({layout} form), first: '{unexpected[0]}'")
+    module.load_state_dict(sd, strict=True)
+    return layout
+
+
 def load_sd_checkpoint(path, unet=None, vae=None, text_encoder=None, location="cpu"):
     """`load_unet_weights`' sibling for a FULL SD-1.5 state dict (CompVis lineage): routes `model.diffusion_model.*` to `unet`,
     `first_stage_model.*` to `vae` and `cond_stage_model.*` to `text_encoder` (a FrozenCLIPEmbedder); a part given as None is skipped.

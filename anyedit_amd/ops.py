@@ -1233,6 +1233,176 @@ def attention_masked_short(q, k, v, mask, B, H, N, D, scale, q_strides, k_stride
     return out
 
 
+# --------------------------------------------------------------------------- GroundingDINO query selection / decoder (csrc/gdino_decoder.hip)
+CONTRASTIVE_MAX_TEXT = 256
+CONTRASTIVE_MAX_C = 256
+TOPK_MAX_K = 1024
+
+
+def _mask2(m, name, B, n):
+    if m.dtype == torch.bool:
+        m = m.view(torch.uint8)
+    _chk(m, torch.uint8, name, 2)
+    if tuple(m.shape) != (B, n) or not m.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous [{B}, {n}] bool / uint8 tensor, got {tuple(m.shape)}")
+    return m
+
+
+def contrastive(x, y, token_mask=None, max_text_len=None, want_logits=True, want_rowmax=False, logits=None, rowmax=None):
+    """ContrastiveEmbed.forward (utils.py:233-268) and / or its row maximum (transformer.py:295).  x bf16 [B, N, C] (unit inner stride, one row
+    stride over all samples), y bf16 [B, T, C] contiguous, token_mask bool / uint8 [B, T], True = a USED token (the reference's text_token_mask).
+    Returns (logits, rowmax), either None when not asked for: logits fp32 [B, N, max_text_len] with -inf at unused tokens and at columns
+    T .. max_text_len-1, rowmax fp32 [B, N] (-inf when a sample has no used token).  With want_logits=False no B*N*T buffer exists.
+    C % 32 == 0, C <= 256, 1 <= T <= max_text_len <= 256."""
+    _chk(x, BF16, "contrastive.x", 3)
+    _chk(y, BF16, "contrastive.y", 3)
+    B, N, C = x.shape
+    T = y.shape[1]
+    max_text_len = T if max_text_len is None else int(max_text_len)
+    if C % 32 or not 32 <= C <= CONTRASTIVE_MAX_C:
+        raise ValueError(f"contrastive: C={C} must be a multiple of 32, at most {CONTRASTIVE_MAX_C}")
+    if not 1 <= T <= max_text_len <= CONTRASTIVE_MAX_TEXT:
+        raise ValueError(f"contrastive: need 1 <= T={T} <= max_text_len={max_text_len} <= {CONTRASTIVE_MAX_TEXT}")
+    if N < 1:
+        raise ValueError("contrastive: no rows")
+    if tuple(y.shape) != (B, T, C) or not y.is_contiguous():
+        raise ValueError(f"contrastive: y must be a contiguous [{B}, {T}, {C}] tensor, got {tuple(y.shape)}")
+    ldx = _rows3(x, "contrastive.x", B, N, C)
+    if token_mask is not None:
+        token_mask = _mask2(token_mask, "contrastive.token_mask", B, T)
+    want_logits = want_logits or logits is not None
+    want_rowmax = want_rowmax or rowmax is not None
+    if not (want_logits or want_rowmax):
+        raise ValueError("contrastive: neither logits nor rowmax is asked for")
+    ldl = 0
+    if want_logits:
+        if logits is None:
+            logits = torch.empty(B, N, max_text_len, dtype=torch.float32, device=x.device)
+        _chk(logits, torch.float32, "contrastive.logits", 3)
+        if tuple(logits.shape) != (B, N, max_text_len) or logits.stride(2) != 1 or (B > 1 and logits.stride(0) != N * logits.stride(1)):
+            raise ValueError(f"contrastive: logits must be [{B}, {N}, {max_text_len}] rows with unit inner stride and one row stride")
+        ldl = logits.stride(1)
+    if want_rowmax:
+        if rowmax is None:
+            rowmax = torch.empty(B, N, dtype=torch.float32, device=x.device)
+        _chk(rowmax, torch.float32, "contrastive.rowmax", 2)
+        if tuple(rowmax.shape) != (B, N) or not rowmax.is_contiguous():
+            raise ValueError(f"contrastive: rowmax must be a contiguous [{B}, {N}] tensor")
+    check(lib.ae_contrastive_bf16(_p(x), ldx, _p(y), _p(token_mask), _p(logits), ldl, _p(rowmax), B, N, T, C, max_text_len, _s()), "ae_contrastive_bf16")
+    return logits, rowmax
+
+
+def topk_rows_max_n():
+    """Largest row length `topk_rows` takes (ae_topk_rows_max_n)."""
+    return lib.ae_topk_rows_max_n()
+
+
+def topk_rows(scores, k, out=None):
+    """int32 [B, k]: the first k indices of torch.sort(scores, dim=1, descending=True, stable=True) — descending value, equal values by ascending
+    index, -0.0 == +0.0, -inf an ordinary value, NaN of either sign above +inf.  scores fp32 [B, N] (unit inner stride).  torch.topk promises no
+    order among ties; query selection meets ties on every masked image row.  1 <= k <= min(N, 1024), N <= topk_rows_max_n()."""
+    _chk(scores, torch.float32, "topk_rows.scores", 2)
+    B, N = scores.shape
+    k = int(k)
+    if B < 1 or N < 1 or scores.stride(1) != 1:
+        raise ValueError(f"topk_rows: scores must be a non-empty [B, N] tensor with unit inner stride, got {tuple(scores.shape)}")
+    if not 1 <= k <= min(N, TOPK_MAX_K):
+        raise ValueError(f"topk_rows: k={k} must be in [1, min(N={N}, {TOPK_MAX_K})]")
+    if N > topk_rows_max_n():
+        raise ValueError(f"topk_rows: N={N} is above the largest supported row length {topk_rows_max_n()}")
+    if out is None:
+        out = torch.empty(B, k, dtype=torch.int32, device=scores.device)
+    _chk(out, torch.int32, "topk_rows.out", 2)
+    if tuple(out.shape) != (B, k) or not out.is_contiguous():
+        raise ValueError(f"topk_rows: out must be a contiguous int32 [{B}, {k}] tensor")
+    check(lib.ae_topk_rows_f32(_p(scores), scores.stride(0) if B > 1 else N, _p(out), B, N, k, _s()), "ae_topk_rows_f32")
+    return out
+
+
+def gdino_proposals(padding_mask, spatial_shapes, proposals=None, keep=None):
+    """gen_encoder_output_proposals (utils.py:56-116, learnedwh=None) in one launch.  padding_mask bool / uint8 [B, N], True = padding;
+    spatial_shapes: a HOST sequence of (H, W) per level with sum H*W == N (at most 8 levels).  Returns (proposals fp32 [B, N, 4] un-sigmoided,
+    +inf on padded rows and rows outside 0.01 < p < 0.99; keep uint8 [B, N], 1 where the row's memory is kept)."""
+    shapes = [(int(h), int(w)) for h, w in spatial_shapes]
+    L = len(shapes)
+    if padding_mask.dim() != 2:
+        raise ValueError(f"gdino_proposals: padding_mask must be [B, N], got {tuple(padding_mask.shape)}")
+    B, N = padding_mask.shape
+    padding_mask = _mask2(padding_mask, "gdino_proposals.padding_mask", B, N)
+    if not 1 <= L <= 8 or any(h < 1 or w < 1 for h, w in shapes) or sum(h * w for h, w in shapes) != N:
+        raise ValueError(f"gdino_proposals: {L} levels {shapes} do not tile N={N} tokens (1 to 8 levels, each at least 1x1)")
+    starts, cur = [], 0
+    for h, w in shapes:
+        starts.append(cur)
+        cur += h * w
+    if proposals is None:
+        proposals = torch.empty(B, N, 4, dtype=torch.float32, device=padding_mask.device)
+    if keep is None:
+        keep = torch.empty(B, N, dtype=torch.uint8, device=padding_mask.device)
+    _chk(proposals, torch.float32, "gdino_proposals.proposals", 3)
+    _chk(keep, torch.uint8, "gdino_proposals.keep", 2)
+    if tuple(proposals.shape) != (B, N, 4) or not proposals.is_contiguous() or tuple(keep.shape) != (B, N) or not keep.is_contiguous():
+        raise ValueError(f"gdino_proposals: proposals must be contiguous [{B}, {N}, 4], keep contiguous [{B}, {N}]")
+    c_shapes = (ctypes.c_int * (2 * L))(*[v for hw in shapes for v in hw])
+    c_starts = (ctypes.c_int * L)(*starts)
+    check(lib.ae_gdino_proposals_f32(_p(padding_mask), c_shapes, c_starts, L, _p(proposals), _p(keep), B, N, _s()), "ae_gdino_proposals_f32")
+    return proposals, keep
+
+
+def gdino_query_sine(reference_points, valid_ratios, ref_input=None, embed=None):
+    """reference_points fp32 [B, nq, 4] (sigmoid boxes), valid_ratios fp32 [B, L, 2] -> (reference_points_input fp32 [B, nq, L, 4]
+    (transformer.py:667-671), gen_sineembed_for_position of its level-0 slice as bf16 rows [B*nq, 512] in (y, x, w, h) order (utils.py:204-230))."""
+    _chk(reference_points, torch.float32, "gdino_query_sine.reference_points", 3)
+    _chk(valid_ratios, torch.float32, "gdino_query_sine.valid_ratios", 3)
+    B, nq, four = reference_points.shape
+    L = valid_ratios.shape[1]
+    if four != 4 or B < 1 or nq < 1 or not reference_points.is_contiguous():
+        raise ValueError(f"gdino_query_sine: reference_points must be a contiguous non-empty [B, nq, 4] tensor, got {tuple(reference_points.shape)}")
+    if tuple(valid_ratios.shape) != (B, L, 2) or L < 1 or L > 64 or not valid_ratios.is_contiguous():
+        raise ValueError(f"gdino_query_sine: valid_ratios must be a contiguous [{B}, L, 2] tensor with 1 <= L <= 64, got {tuple(valid_ratios.shape)}")
+    if ref_input is None:
+        ref_input = torch.empty(B, nq, L, 4, dtype=torch.float32, device=reference_points.device)
+    if embed is None:
+        embed = torch.empty(B * nq, 512, dtype=BF16, device=reference_points.device)
+    _chk(ref_input, torch.float32, "gdino_query_sine.ref_input", 4)
+    _chk(embed, BF16, "gdino_query_sine.embed", 2)
+    if tuple(ref_input.shape) != (B, nq, L, 4) or not ref_input.is_contiguous() or tuple(embed.shape) != (B * nq, 512) or embed.stride(1) != 1:
+        raise ValueError(f"gdino_query_sine: ref_input must be contiguous [{B}, {nq}, {L}, 4], embed [{B * nq}, 512] rows with unit inner stride")
+    check(lib.ae_gdino_query_sine(_p(reference_points), _p(valid_ratios), _p(ref_input), _p(embed), embed.stride(0), B, nq, L, _s()), "ae_gdino_query_sine")
+    return ref_input, embed
+
+
+def gdino_box_refine(h, w3, b3, ref, ref_is_logit=False, want_unsigmoid=False, boxes=None, unsigmoid=None):
+    """The last layer of a box MLP plus the anchor update (transformer.py:721-724, groundingdino.py:322-324): h fp32 [M, 256] (unit inner stride),
+    w3 fp32 [4, 256], b3 fp32 [4], ref fp32 [M, 4] -> boxes = sigmoid(u), u = h w3^T + b3 + inverse_sigmoid(ref) (eps 1e-3), all fp32.
+    ref_is_logit: ref is already un-sigmoided (it may be +inf: the box is then 1.0) and is added as it is (transformer.py:296-306).
+    Returns boxes, or (boxes, u) with want_unsigmoid."""
+    _chk(h, torch.float32, "gdino_box_refine.h", 2)
+    _chk(w3, torch.float32, "gdino_box_refine.w3", 2)
+    _chk(b3, torch.float32, "gdino_box_refine.b3", 1)
+    _chk(ref, torch.float32, "gdino_box_refine.ref", 2)
+    M = h.shape[0]
+    if M < 1 or h.shape[1] != 256 or h.stride(1) != 1:
+        raise ValueError(f"gdino_box_refine: h must be a non-empty [M, 256] tensor with unit inner stride, got {tuple(h.shape)}")
+    if tuple(w3.shape) != (4, 256) or not w3.is_contiguous() or b3.numel() != 4 or not b3.is_contiguous():
+        raise ValueError("gdino_box_refine: w3 must be contiguous [4, 256] and b3 hold 4 values")
+    if tuple(ref.shape) != (M, 4) or not ref.is_contiguous():
+        raise ValueError(f"gdino_box_refine: ref must be a contiguous [{M}, 4] tensor, got {tuple(ref.shape)}")
+    if boxes is None:
+        boxes = torch.empty(M, 4, dtype=torch.float32, device=h.device)
+    want_unsigmoid = want_unsigmoid or unsigmoid is not None
+    if want_unsigmoid and unsigmoid is None:
+        unsigmoid = torch.empty(M, 4, dtype=torch.float32, device=h.device)
+    for t, n in ((boxes, "boxes"), (unsigmoid, "unsigmoid")):
+        if t is not None:
+            _chk(t, torch.float32, "gdino_box_refine." + n, 2)
+            if tuple(t.shape) != (M, 4) or not t.is_contiguous():
+                raise ValueError(f"gdino_box_refine: {n} must be a contiguous [{M}, 4] tensor")
+    check(lib.ae_gdino_box_refine_f32(_p(h), h.stride(0), _p(w3), _p(b3), _p(ref), _p(boxes), _p(unsigmoid), M, 1 if ref_is_logit else 0, _s()),
+          "ae_gdino_box_refine_f32")
+    return (boxes, unsigmoid) if want_unsigmoid else boxes
+
+
 def rows_to_nchw_out(x, out):
     """channels-last bf16 rows [B*H*W, C] contiguous -> the given [B, C, H, W] buffer (fp32 or bf16, contiguous): `rows_to_nchw` into a
     buffer the caller owns (no allocation)."""

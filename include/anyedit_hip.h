@@ -543,6 +543,45 @@ int ae_attn_masked_short_bf16(const void* q, const void* k, const void* v, const
                               long q_sn, long k_sb, long k_sh, long k_sn, long v_sb, long v_sh, long v_sn, long o_sb, long o_sh, long o_sn, float scale,
                               void* stream);
 
+/* ---- GroundingDINO's query selection, decoder and heads (GroundingDINO/groundingdino/models/GroundingDINO/transformer.py:284-327 two-stage query
+ * selection, :598-735 TransformerDecoder, :802-927 DeformableTransformerDecoderLayer; groundingdino.py:317-335 heads).  Self- and text
+ * cross-attention are ae_attn_fwd_bf16 (head_dim 32, key mask), the deformable cross-attention ae_linear_f32 + ae_ms_deform_attn_fwd_f32 +
+ * ae_scale_residual_f32_bf16, projections and feed-forwards ae_gemm_bf16, LayerNorms ae_layernorm_bf16; these are the rest
+ * (csrc/gdino_decoder.hip).  No atomics, no scratch, no host synchronisation; every launch is deterministic.  Divisions are IEEE and logf / expf /
+ * sinf / cosf the library's own, no fast-math variants: validity flags depend on fp32 values bit for bit.
+ * ae_contrastive_bf16: ContrastiveEmbed.forward (utils.py:233-268) and / or its row maximum (transformer.py:291-295).  x bf16 rows, row n of sample b
+ *   at (b*N + n) * ldx, C wide; y bf16 [B, T, C] contiguous; token_mask uint8 [B, T] or null, NON-ZERO = a USED token (the reference's
+ *   text_token_mask).  logits (may be null) fp32, row (b*N + n) * ldl, max_text_len wide: x_n . y_t for used t < T, -inf for unused tokens and for
+ *   columns T .. max_text_len-1 (:262-266).  rowmax (may be null) fp32 [B, N]: the maximum of that row, bit-equal to the maximum of the logits a call
+ *   with both outputs stores; -inf when the sample has no used token.  With logits null nothing of size B*N*T is written or allocated.  MFMA on the
+ *   bf16 operands, fp32 accumulation.  C % 32 == 0, C <= 256, 1 <= T <= max_text_len <= 256, N >= 1, B <= 65535, ldx % 8 == 0, x / y / logits
+ *   16-byte aligned; the rest is refused.  The text rows are streamed through LDS in tiles of 64 tokens (33 856 bytes).
+ * ae_topk_rows_f32: out int32 [B, k] = the first k indices of torch.sort(scores, dim=1, descending=True, stable=True) (transformer.py:301 with a
+ *   defined order among ties): descending value, equal values by ascending index; -0.0 == +0.0; -inf entries are ordinary values; NaN of either
+ *   sign orders above +inf and all NaNs are equal.  scores fp32, row b at b * ld.  1 <= k <= min(N, 1024), N <= ae_topk_rows_max_n() = 2^24.  One
+ *   workgroup per row: radix select of the k-th key bit by bit, compaction in index order, rank sort in LDS.
+ * ae_gdino_proposals_f32: gen_encoder_output_proposals (utils.py:56-116, learnedwh=None).  padding_mask uint8 [B, N], NON-ZERO = padding;
+ *   shapes_hw / level_start: HOST arrays int [L, 2] / [L] (checked against each other and N, L <= 8).  proposals fp32 [B, N, 4]: log(p / (1 - p))
+ *   of p = ((x + 0.5) / valid_W, (y + 0.5) / valid_H, 0.05 * 2^lvl, 0.05 * 2^lvl) (:86, :92, :105), valid_H / valid_W counted on the level's first
+ *   column / first row (:74-75); padded rows and rows with a coordinate outside 0.01 < p < 0.99 hold +inf in all four (:102-107).  keep uint8
+ *   [B, N]: 1 where the row is neither (the rows whose memory :110-111 keeps).  A valid extent of 0 gives +inf, not a fault.
+ * ae_gdino_query_sine: ref fp32 [B, nq, 4] sigmoid boxes, valid_ratios fp32 [B, L, 2] -> ref_input fp32 [B, nq, L, 4] = ref[:, :, None] *
+ *   cat([valid_ratios, valid_ratios], -1)[:, None] (transformer.py:667-671), and embed bf16 rows (b*nq + q) * lde, 512 wide =
+ *   gen_sineembed_for_position(ref_input[:, :, 0, :]) (utils.py:204-230) in its (y, x, w, h) order.  lde >= 512, even.
+ * ae_gdino_box_refine_f32: the last layer of a box MLP and the anchor update (transformer.py:721-724, groundingdino.py:322-324): h fp32 [M, 256]
+ *   row stride ldh, w3 fp32 [4, 256], b3 fp32 [4], ref fp32 [M, 4]:  u = (h w3^T + b3) + inverse_sigmoid(ref) (util/misc.py:704, eps = 1e-3),
+ *   boxes = sigmoid(u) fp32 [M, 4]; u_out (may be null) receives u.  ref_is_logit != 0 (transformer.py:296-306): ref is already un-sigmoided, may
+ *   be +inf, and is added as it is (+inf gives a box of 1.0).                                                                                   */
+int ae_contrastive_bf16(const void* x, long ldx, const void* y, const void* token_mask, float* logits, long ldl, float* rowmax, int B, int N, int T, int C,
+                        int max_text_len, void* stream);
+int ae_topk_rows_max_n(void);
+int ae_topk_rows_f32(const float* scores, long ld, int* out, int B, int N, int k, void* stream);
+int ae_gdino_proposals_f32(const void* padding_mask, const int* shapes_hw, const int* level_start, int L, float* proposals, void* keep, int B, int N,
+                           void* stream);
+int ae_gdino_query_sine(const float* ref, const float* valid_ratios, float* ref_input, void* embed, long lde, int B, int nq, int L, void* stream);
+int ae_gdino_box_refine_f32(const float* h, long ldh, const float* w3, const float* b3, const float* ref, float* boxes, float* u_out, long M, int ref_is_logit,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
