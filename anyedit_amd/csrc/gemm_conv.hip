@@ -29,13 +29,6 @@ namespace {
 #ifndef AE_CONV_SPEC
 #define AE_CONV_SPEC 1   // round 4: on (prepared in round 3, measured at the start of round 4: 40 checksums identical, UNet step 13.47 -> 13.44 ms over three alternating runs, profiles/r04_v2_cspec_ab.txt)
 #endif
-#ifndef AE_GEMM_WA_DEFAULT
-#define AE_GEMM_WA_DEFAULT 3
-#endif
-#ifndef AE_GEMM_PP_DEFAULT
-#define AE_GEMM_PP_DEFAULT 63   // 15 + the slab form of the conv loop (16 un-split, 32 split-K): outputs bit-identical (56 checksums), every launch of the family 1-3 % faster
-                                // un-graphed, UNet step -0.02 ms over three alternating A/B rounds on two boxes (profiles/r04_v24..v26_lnfold_slab_ab.txt)
-#endif
 #ifndef AE_XE_OCC
 #define AE_XE_OCC 4         // waves per SIMD the 128x128 LayerNorm-fold instantiations must leave room for (two 8-wave blocks per CU); 0 = unconstrained (A/B builds)
 #endif
@@ -92,9 +85,6 @@ struct GemmArgs {
     // (the split-K index of a launch that does not split) multiplies against weight set `par` ([N, 4 CinPad] each, K ordered (tap, channel) with tap =
     // 2 i + j over the window rows / columns) and scatters its rows to the parity's pixels of the [B, 2H, 2W] output.
     int sub2;
-    // split-K launches only: 1 = stop at the fp32 partials (no splitk_reduce_kernel launch): the consumer folds the K ranges itself (ae_groupnorm_splitk_nhwc_bf16:
-    // the GroupNorm of the 16x16 / 8x8 levels reads the partials instead of the reduced tensor — one launch and one round trip of the activation less)
-    int defer_reduce;
 };
 
 // LDS-DMA: one wave moves 64 x 16 B from global straight into LDS at (wave-uniform dst) + lane*16.  The builtin exists only
@@ -136,10 +126,6 @@ constexpr int epilogue_passes(int FM, int bytes_per_frag_row, int lds_bytes) {
     return FM;
 }
 
-// WAVES_K = 2: two groups of WAVES_M x WAVES_N waves split every 64-deep K tile between them (32 each) and are summed through
-// LDS once at the end.  Same thread count and staging as an 8-wave block, but each wave owns a 2x larger output tile, so the
-// block issues a third fewer LDS fragment reads per MFMA (the 128x128 tile is LDS-bound: with 15/16 of its MFMAs removed it
-// still takes 73 % of the time).
 // CS = true: the epilogue also emits the per-channel statistics of its output (GemmArgs::colstats).  The wave tile is then staged in
 // 32-row passes (one statistics slab per pass) and the output loop gives every lane a FIXED 8-column chunk, so a lane can carry the
 // column sums of its rows in registers; the R = 64 / (WN / 8) row-lanes of a chunk are folded through the wave's own staging slice.
@@ -147,9 +133,8 @@ constexpr int epilogue_passes(int FM, int bytes_per_frag_row, int lds_bytes) {
 // the K-step time of these kernels (~4600 cycles for the 64 KiB of a 192x320 step, ~2100 for the 32 KiB of a 128x128 step = bytes /
 // ~14 B/clk/CU) is the LDS-DMA path's rate.  It is not that simple: 192x320 conv 87.8 -> 92.6 us (A through registers) / 96.2 (W),
 // 128x128 conv 105.9 -> 115.9 / 118.1, dense 128x128 +3..+10 %, UNet step 14.44 -> 14.51-14.60 ms (profiles/r03_v3_hybrid_loader.txt).)
-// WA (round 3): operand-ahead loop on the two-stage LDS-DMA pipeline — 1: three W stages (weights two K tiles ahead), 2: three A stages
-// (activations two tiles ahead); counted vmcnt + raw s_barrier instead of the per-step drain, unrolled by six so that every stage index is a
-// constant.  See the comment at the loop, DESIGN.md §7a and profiles/r03_v30_weights_ahead.txt.
+// WA (round 3): operand-ahead loop on the two-stage LDS-DMA pipeline — 1: three W stages (weights two K tiles ahead); counted vmcnt + raw
+// s_barrier instead of the per-step drain, unrolled by six so that every stage index is a constant.  (2, three A stages, is superseded by 3 / 4.)  See the comment at the loop, DESIGN.md §7a and profiles/r03_v30_weights_ahead.txt.
 // LAB (AE_GEMM_LAB builds only, tools/ubench): 1 = no DMA after the first tile, 2 = no LDS reads / MFMAs, 3 = MFMAs on stale registers (no LDS reads)
 // XE (round 4): 1 = the epilogue also emits per-row (sum, sum of squares) of its bf16 output per 64-column slice (GemmArgs::rowstats), 2 = the
 // epilogue applies the LayerNorm fold from such statistics of A (GemmArgs::ln_stats / ln_colsum).  XE = 0 instantiations are unchanged code.
@@ -163,10 +148,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WAVES_K, (XE == 2 && BM ==
     static_assert(XE != 1 || BN / WAVES_N == 64, "row statistics are emitted per 64-column slice = one wave tile's width");
     static_assert(STAGES == 2 || (GLDS && WAVES_K == 1), "the deep LDS ring exists only for the LDS-DMA loader");
     static_assert(!WA || (GLDS && STAGES == 2 && WAVES_K == 1), "operand-ahead is a variant of the two-stage LDS-DMA pipeline");
-    static_assert(WA >= 0 && WA <= 4, "WA: 0 none, 1 weights two tiles ahead (three W stages), 2 activations two tiles ahead (three A stages), 3 ping-pong (two wave groups one barrier apart), 4 ping-pong over an activation slab per (channel chunk, ky)");
+    static_assert(WA == 0 || WA == 1 || WA == 3 || WA == 4, "WA: 0 none, 1 weights two tiles ahead (three W stages), 3 ping-pong (two wave groups one barrier apart), 4 ping-pong over an activation slab per (channel chunk, ky)");
     static_assert(WA < 3 || 64 * WAVES_M * WAVES_N * WAVES_K == 512, "the ping-pong loops pair wave w with wave w + 4 (one SIMD's two waves)");
     static_assert(WA != 4 || (AMODE == A_CONV3 && GLDS && BM % 16 == 0), "the slab loop is a 3x3-convolution loop");
-    static_assert(WAVES_K == 1 || WAVES_K == 2, "K groups: 1 or 2");
+    static_assert(WAVES_K == 1, "one K group per block (the two-group form is removed: DESIGN.md, \"Built, measured, removed\")");
     constexpr int NT = 64 * WAVES_M * WAVES_N * WAVES_K;
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;  // wave tile
     constexpr int FM = WM / 16, FN = WN / 16;            // 16x16 fragments per wave
@@ -175,7 +160,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WAVES_K, (XE == 2 && BM ==
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];  // 2 * (BM + BN) * BK bf16 (dynamic: > 64 KiB for 128x160)
     bf16_t* const smem = reinterpret_cast<bf16_t*>(smem_raw);
     bf16_t* sA = smem;
-    bf16_t* sB = smem + (WA >= 2 ? 3 : STAGES) * BM * BK;
+    bf16_t* sB = smem + (WA >= 3 ? 3 : STAGES) * BM * BK;
 
     // The wave index as a SCALAR (v_readfirstlane once): tid >> 6 is wave-uniform but lives in a VGPR, and every LDS-DMA destination derived
     // from it then costs a v_readfirstlane_b32 per piece per K step in front of its s_mov m0 (48-66 per six steps of the operand-ahead loops;
@@ -198,7 +183,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WAVES_K, (XE == 2 && BM ==
     const bool lab_me = blockIdx.x == gridDim.x / 2 && lane == 0 && (wave == 0 || wave == 4);
     const int lab_base = wave == 0 ? 0 : 16;
 #endif
-    const int wk = wave / (WAVES_M * WAVES_N), wmn = wave % (WAVES_M * WAVES_N);  // K group, position inside the group
+    const int wk = wave / (WAVES_M * WAVES_N), wmn = wave % (WAVES_M * WAVES_N);  // K group (0: see `writer`), position inside the group
     const int wm = wmn / WAVES_N, wn = wmn % WAVES_N;
     const int l15 = lane & 15, lg = lane >> 4;
     const int ntn = (p.N + BN - 1) / BN, ntm = (p.M + BM - 1) / BM;
@@ -456,7 +441,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WAVES_K, (XE == 2 && BM ==
         const bf16_t* cB = sB + (curB < 0 ? cur : curB) * BN * BK + (wn * WN) * BK;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            if (WAVES_K == 2 && kk != wk) continue;  // wave-uniform: this K half belongs to the other group
             bf16x8_t af[FM], bfr[FN];
             const int ch = kk * 4 + lg;
 #pragma unroll
@@ -512,14 +496,11 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WAVES_K, (XE == 2 && BM ==
         // LDS stage — no staging VGPRs, no ds_write_b128 pass (the slowest LDS instruction, ~79 B/clk/CU).  The LDS image is
         // lane-linear, so the XOR swizzle is applied to the per-lane SOURCE chunk instead (same involution as the ds_read
         // side).  hipcc drains the DMA (vmcnt(0)) in front of each __syncthreads().
-        // conv: this tap's per-lane gather offset (OOB for halo pixels).  The offsets are VGPR operands of the DMA pieces, and hipcc waits
-        // for the pieces that read a register before it rewrites it: WA 2 (A tiles two ahead) therefore rotates three register sets with the
-        // A stages — the set rewritten in step kt was last read by pieces issued three steps earlier, long landed.
-        int fa_cur[WA == 2 ? 3 : 1][A_CH];
+        // conv: this tap's per-lane gather offset (OOB for halo pixels)
+        int fa_cur[A_CH];
         // (always_inline: out of line, the by-reference captures — ld_tap, ld_ci, fa_cur — live in scratch memory, and a scratch load inside the
         // loop is a VMEM operation hipcc waits for with vmcnt(0): it drained the whole DMA queue once per step in the unrolled operand-ahead loop)
         auto dma_a = [&](int kt, int buf) __attribute__((always_inline)) {
-            const int fs = WA == 2 ? buf : 0;
             const int k0 = (kt_begin + kt) * BK;
             if (AMODE == A_DENSE) {
                 const bool second = k0 >= p.Ksplit;
@@ -543,31 +524,28 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WAVES_K, (XE == 2 && BM ==
                 // operand-ahead loops and deep rings: the (tap, channel) position is derived from kt — carried as loop state (ld_tap / ld_ci, captured by
                 // reference) it ended up in scratch memory in the unrolled loop, and every scratch load is a VMEM operation hipcc waits for
                 // with vmcnt(0): the whole DMA queue drained once per step
-                // AE_CONV_SPEC (build variant, prepared for an A/B): the activations-ahead conv instantiation is only launched for chunk-major K and
-                // no upsample, so both run-time flags fold away — no generic division for the tap-major position, no per-piece upsample branch
-                constexpr bool KM1 = AE_CONV_SPEC && WA == 2;
                 int cur_tap = ld_tap, cur_ci = ld_ci;
                 constexpr bool STATELESS = true;   // (the two-stage loops too: their scratch load of the tap state sat in front of every step's DMA issue)
                 if (STATELESS) {
                     const int lin = kt_begin + kt;
-                    if (KM1 || p.kmajor) { cur_tap = lin % 9; cur_ci = (lin / 9) * BK; }
+                    if (p.kmajor) { cur_tap = lin % 9; cur_ci = (lin / 9) * BK; }
                     else if (AE_CONV_SPEC) {   // tap-major: lin / per by the reciprocal set up once in front of the loops (exact for lin < 2^16, per <= 64)
                         cur_tap = conv_per == 1 ? lin : (int)__umulhi((unsigned)lin, conv_per_magic);
                         cur_ci = (lin - cur_tap * conv_per) * BK;
                     } else { const int per = p.CinPad / BK; cur_tap = lin / per; cur_ci = (lin - cur_tap * per) * BK; }
                 }
                 // sub2: cur_tap counts the 2 x 2 window's taps; (ky, kx) is the tap's place in the 3 x 3 frame the masks and offsets are laid out for
-                const int ky = (!KM1 && p.sub2) ? py + (cur_tap >> 1) : cur_tap / 3, kx = (!KM1 && p.sub2) ? px + (cur_tap & 1) : cur_tap - ky * 3;
-                const int mbit = (!KM1 && p.sub2) ? ky * 3 + kx : cur_tap;
-                if (cur_ci == 0 || kt == 0 || KM1 || p.kmajor || WA == 2) {  // a new tap: the per-lane part (halo mask, upsample source pixel) changes only here
+                const int ky = p.sub2 ? py + (cur_tap >> 1) : cur_tap / 3, kx = p.sub2 ? px + (cur_tap & 1) : cur_tap - ky * 3;
+                const int mbit = p.sub2 ? ky * 3 + kx : cur_tap;
+                if (cur_ci == 0 || kt == 0 || p.kmajor) {  // a new tap: the per-lane part (halo mask, upsample source pixel) changes only here
 #pragma unroll
                     for (int i = 0; i < A_CH; ++i) {
                         int src = fa_off[i] + ((ky * p.Wd + kx) * p.Cin) * 2;  // >= 0 for every in-image tap (voffset is bounds-checked unsigned)
-                        if (!KM1 && p.ups) {  // nearest-x2 upsample folded into the gather: source pixel = virtual pixel >> 1 (3 of 64 convs per UNet call)
+                        if (p.ups) {  // nearest-x2 upsample folded into the gather: source pixel = virtual pixel >> 1 (3 of 64 convs per UNet call)
                             const int cc = ((tid + i * NT) & 7) ^ (((tid + i * NT) >> 3) & 7);
                             src = (int)((a_base[i] + (long)(max(a_iy[i] + ky, 0) >> 1) * p.Wd + (max(a_ix[i] + kx, 0) >> 1)) * p.Cin + cc * 8) * 2;
                         }
-                        fa_cur[fs][i] = ((fa_mask[i] >> mbit) & 1u) ? src : OOB;
+                        fa_cur[i] = ((fa_mask[i] >> mbit) & 1u) ? src : OOB;
                     }
                 }
                 const int tap_off = cur_ci * 2;  // wave-uniform -> SGPR offset
@@ -575,7 +553,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WAVES_K, (XE == 2 && BM ==
 #pragma unroll
                 for (int i = 0; i < A_CH; ++i) {
                     bf16_t* dst = sA + buf * BM * BK + (wave + (NT / 64) * i) * 8 * BK;
-                    lds_dma16(rsA, dst, fa_cur[fs][i], tap_off);
+                    lds_dma16(rsA, dst, fa_cur[i], tap_off);
                 }
                 }
                 if (STATELESS) {
@@ -911,17 +889,15 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WAVES_K, (XE == 2 && BM ==
             }
 #endif
         } else if constexpr (WA != 0) {
-            // One operand two tiles ahead (three stages of it, two of the other), for the operand that arrives COLD inside a UNet evaluation:
-            //   WA 1: the weights (32x32 / 8x8 levels: a layer's weights come from HBM, its activations from L2 / the Infinity Cache;
-            //         tools/cold_weight_probe.py: cold weights cost those launches 5-11 %);
-            //   WA 2: the activations (64x64 level on the 192x320 tile: 31-126 MB tensors that no cache holds; 3 x 24 + 2 x 40 = 152 KiB).
-            // Per step the near operand's tile of step kt + 1 and then the far operand's tile of step kt + 2 are issued; DMA pieces retire in
+            // The weights two tiles ahead (three stages of them, two of the activations): inside a UNet evaluation a layer's weights arrive COLD
+            // (32x32 / 8x8 levels: from HBM, the activations from L2 / the Infinity Cache; tools/cold_weight_probe.py: cold weights cost those
+            // launches 5-11 %).
+            // Per step the activation tile of step kt + 1 and then the weight tile of step kt + 2 are issued; DMA pieces retire in
             // issue order, so vmcnt(FAR pieces) at the end of the step proves everything of step kt + 1 has landed while the far tile of
             // step kt + 2 keeps flying.  The loop is unrolled by six (lcm of the ring lengths): every stage index is a constant (with a
             // run-time index hipcc cannot tell the stages apart and waits for the fresh pieces in front of the step's own LDS reads).
-            constexpr int FAR = WA == 1 ? B_CH : A_CH;
-            if (WA == 1) { dma_a(0, 0); dma_w(0, 0); if (KT > 1) dma_w(1, 1); }
-            else { dma_w(0, 0); dma_a(0, 0); if (KT > 1) dma_a(1, 1); }
+            constexpr int FAR = B_CH;
+            dma_a(0, 0); dma_w(0, 0); if (KT > 1) dma_w(1, 1);
             if (KT > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(FAR) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             xe_mid();
@@ -932,15 +908,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WAVES_K, (XE == 2 && BM ==
                     const int kt = kt0 + u;
                     if (kt >= KT) break;
                     const int near_cur = u & 1, far_cur = u % 3, far_next = (u + 2) % 3;   // far_next: the stage read in step kt - 1
-                    if (WA == 1) {
-                        if (kt + 1 < KT) dma_a(kt + 1, near_cur ^ 1);
-                        if (kt + 2 < KT) dma_w(kt + 2, far_next);
-                        compute_tile(near_cur, far_cur);
-                    } else {
-                        if (kt + 1 < KT) dma_w(kt + 1, near_cur ^ 1);
-                        if (kt + 2 < KT) dma_a(kt + 2, far_next);
-                        compute_tile(far_cur, near_cur);
-                    }
+                    if (kt + 1 < KT) dma_a(kt + 1, near_cur ^ 1);
+                    if (kt + 2 < KT) dma_w(kt + 2, far_next);
+                    compute_tile(near_cur, far_cur);
                     if (kt + 2 < KT) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(FAR) : "memory");
                     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -990,29 +960,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WAVES_K, (XE == 2 && BM ==
         }
     }
 
-    if (WAVES_K == 2) {
-        // sum the two K groups: group 1 parks its accumulators in LDS (the ring is free: the loop ended on a barrier), group 0 adds
-        f32x4* red = reinterpret_cast<f32x4*>(smem_raw) + (long)wmn * FM * FN * 64 + lane;
-        static_assert(WAVES_K == 1 || WAVES_M * WAVES_N * FM * FN * 64 * 16 <= 2 * (BM + BN) * BK * 2, "K-group reduction must fit the ring");
-        if (wk == 1) {
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int j = 0; j < FN; ++j) red[(i * FN + j) * 64] = acc[i][j];
-        }
-        __syncthreads();
-        if (wk == 0) {
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int j = 0; j < FN; ++j) {
-                    const f32x4 o = red[(i * FN + j) * 64];
-                    acc[i][j][0] += o[0]; acc[i][j][1] += o[1]; acc[i][j][2] += o[2]; acc[i][j][3] += o[3];
-                }
-        }
-        __syncthreads();
-    }
-    const bool writer = wk == 0;  // with K groups only group 0 holds the result; group 1 keeps the block's barriers company
+    const bool writer = wk == 0;  // always true with one K group, but hipcc does not fold it: dropping the test halves every instantiation's listing (its own change, to be timed)
 
     // ---- epilogue ---------------------------------------------------------------------------
 #ifdef AE_GEMM_LAB_NOEPI
@@ -1510,13 +1458,9 @@ Plan make_plan(int M, int N, int K, bool can_split) {
     if (!can_split || kt < 32 || t == 0 || t == 3) return {t, 1};
     const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
     const double waste128 = (double)(((N + 127) / 128) * 128) / (double)N;
-    // small conv grids (<= 128 output tiles: 8x8 level, stride-2 convs, training batches): split only until the grid reaches one block
-    // per CU and run those blocks under the three-stage ring, instead of splitting to two blocks per CU.  In situ: M = 768 convs
-    // 46 -> 43 us, inference step unchanged, training step -3 %.  (For 240-tile grids the unsplit ring LOSES: 127 -> 158 us.)
-    static const int conv_deep = getenv("AE_CONV_DEEP") ? atoi(getenv("AE_CONV_DEEP")) : 0;  // round 3: off — with the weights-ahead 128x128 kernel two blocks per CU win again (13.60 -> 13.55 ms, two runs each way)
+    // small 128x128 grids split K until two blocks share every CU (480 blocks)
     if (waste128 <= 1.10 && t128 < 256) {
         int s = force_s > 0 ? force_s : (int)((480 + t128 - 1) / t128);
-        if (conv_deep && force_s <= 0 && t128 <= 128) s = (int)(256 / t128);   // grid <= 256: every block alone on its CU, latency hidden by the ring
         static const int smax = getenv("AE_CONV_SPLIT_MAX") ? atoi(getenv("AE_CONV_SPLIT_MAX")) : 8;   // A/B knob (round 5: 16 for the M = 256 convs of a training batch)
         if (s > smax) s = smax;
         if (s > kt / 8) s = kt / 8;
@@ -1569,15 +1513,8 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
     if (pick == 3 && (!t160 || AMODE == A_DENSE || a.epi == EPI_GEGLU || a.splitk > 1)) pick = 1;
     // 8-wave (4x2) blocks: twice the waves per CU at the same LDS footprint -> twice the latency tolerance of the
     // one-tile-ahead pipeline.  Measured on MI355X (profiles/r01_kbench_w8.txt): dense GEMMs -15..-25 % time, the 128x64 conv
-    // unchanged (+-2 %), so that one keeps 4 waves (larger wave tile, fewer LDS reads per MFMA).  AE_GEMM_W8=0 forces 4 waves.
-    static const int w8 = getenv("AE_GEMM_W8") ? atoi(getenv("AE_GEMM_W8")) : 2;
-    // two K groups of 2x2 waves on the 128x128 tile: pays when the K loop is long enough to amortise the final LDS reduction
-    // (kbench, operands L2-hot: convs with >= 90 K tiles +4..7 %, GEMMs with 10-40 K tiles -5..-25 %).  Inside the UNet evaluation,
-    // where every layer's weights arrive cold, the same rule LOSES 2.5 % of the step (in-situ A/B, one box), so it stays off:
-    // AE_GEMM_WK = 0 off (default), 1 rule, 2 always.
-    static const int wk_knob = getenv("AE_GEMM_WK") ? atoi(getenv("AE_GEMM_WK")) : 0;
+    // unchanged (+-2 %), so that one keeps 4 waves (larger wave tile, fewer LDS reads per MFMA).
     const int kt_block = ((a.K + BK - 1) / BK + a.splitk - 1) / a.splitk;
-    const bool wk_env = wk_knob == 2 || (wk_knob == 1 && AMODE == A_CONV3 && kt_block >= 60);
     const bool conv = AMODE == A_CONV3;
     const char* what = conv ? "ae_conv3x3_bf16" : "ae_gemm_bf16";
     // LDS-DMA loaders need whole-tile decisions: no K tail, no mixed-source tile, no upsample gather / padded channels
@@ -1586,23 +1523,22 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
     if (conv && a.kmajor && !glds) { ae_set_error("%s: the chunk-major K order exists only in the LDS-DMA loader (AE_GEMM_GLDS=0 is set)", what); return AE_ERR_UNSUPPORTED; }
     auto lds_of = [](int bm, int bn, int st) { return (size_t)st * (bm + bn) * BK * sizeof(bf16_t); };
     auto lds_wa = [](int bm, int bn) { return (size_t)(2 * bm + 3 * bn) * BK * sizeof(bf16_t); };  // weights-ahead: two A stages, three W stages
-    // tuning knob (bit flags): weights two tiles ahead on the 8-wave 128x128 two-stage kernel — 1 convs, 2 dense (80 KiB per block: still two
-    // blocks per CU).  Measured (profiles/r03_v30_weights_ahead.txt, final form): 32x32-level conv 640 -> 640 hot 101.9 -> 87.9 us, with the
+    // The 8-wave 128x128 two-stage kernel runs with the weights two tiles ahead (WA = 1; 80 KiB per block: still two blocks per CU), convs and dense.
+    // Measured (profiles/r03_v30_weights_ahead.txt, final form): 32x32-level conv 640 -> 640 hot 101.9 -> 87.9 us, with the
     // weight rotated through a pool larger than the Infinity Cache 113.4 -> 89.6 us; 1920 -> 640: 327 -> 251 us; in situ 126 -> 96 us;
-    // UNet step 14.70 -> 14.33 ms (two runs each way, one box).  Default on for both.
-    static const int wa = getenv("AE_GEMM_WA") ? atoi(getenv("AE_GEMM_WA")) : AE_GEMM_WA_DEFAULT;
+    // UNet step 14.70 -> 14.33 ms (two runs each way, one box).
     // (Round 3's activations-ahead loop on the 192x320 tile — three A stages, the round-3 default for its dense / un-split conv launches: ff2 of the
     // 64x64 level 70.8 -> 63.0 us in situ — is superseded by the ping-pong loop below, which keeps its LDS layout (three A stages + two W stages =
-    // 152 KiB); its instantiations and the AE_GEMM_AA knob are gone, the loop itself remains as the weights-ahead form of the 128x128 kernel.)
+    // 152 KiB); its instantiations are gone, the loop itself remains as the weights-ahead form of the 128x128 kernel.)
 #ifdef AE_GEMM_TRACE
     auto lds_aa = [](int bm, int bn) { return (size_t)(3 * bm + 2 * bn) * BK * sizeof(bf16_t) + 8192; };   // + the trace area
 #else
     auto lds_aa = [](int bm, int bn) { return (size_t)(3 * bm + 2 * bn) * BK * sizeof(bf16_t); };
 #endif
-    // tuning knob (bit flags): the ping-pong main loop (WA = 3, round 4) on the 192x320 tile — 1 un-split convs, 2 split-K convs, 4 dense non-GEGLU,
-    // 8 GEGLU (4 x 2 waves).  Same LDS footprint as the activations-ahead loop (three A stages + two W stages).  16 / 32: the un-split / split-K
-    // convs on the activation-slab form of the loop (WA = 4; two slab stages + two W stages = 132 KiB).
-    static const int pp = getenv("AE_GEMM_PP") ? atoi(getenv("AE_GEMM_PP")) : AE_GEMM_PP_DEFAULT;
+    // The 192x320 tile runs the ping-pong main loop (WA = 3, round 4): un-split and split-K convs, dense non-GEGLU, GEGLU (4 x 2 waves); three A stages +
+    // two W stages.  Stride-1 convs that meet `slab_ok` take its activation-slab form (WA = 4; two slab stages + two W stages = 132 KiB): outputs
+    // bit-identical (56 checksums), every launch of the family 1-3 % faster un-graphed, UNet step -0.02 ms over three alternating A/B rounds on two
+    // boxes (profiles/r04_v24..v26_lnfold_slab_ab.txt).  The nearest-x2 / zero-insert gathers stay on the plain two-stage loop.
     int rc = 0;
 
     // 192x320 tile, one block per CU (128 KiB LDS), 8 waves with 96x80 (or 48x160 for the GEGLU column pairing) wave tiles:
@@ -1634,9 +1570,11 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
     const size_t lds_slab = (size_t)2 * ((192 + 192 / 16 + 1 + 7) / 8) * 1024 + (size_t)2 * 320 * BK * sizeof(bf16_t);
     if (conv && a.splitk > 1 && glds && make_plan(a.M, a.N, a.K, true).tile == 4) {  // split-K under the 192x320 tile (make_plan)
         const long t = (long)(a.M / 192) * (a.N / 320) * a.splitk;
-        if ((pp & 32) && (pp & 2) && slab_ok) { if constexpr (AMODE == A_CONV3) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 4>, (unsigned)t, 512, lds_slab, stream, a, what); }
-        else if ((pp & 2) && !a.ups) { if constexpr (AMODE == A_CONV3) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what); }
-        else rc = launch_kernel(gemm_kernel<192, 320, AMODE, 2, 4, true>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
+        if constexpr (AMODE == A_CONV3) {
+            if (slab_ok) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 4>, (unsigned)t, 512, lds_slab, stream, a, what);
+            else if (!a.ups) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what);
+            else rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
+        }
         done = true;
     }
     if (!done && t320 && glds && a.splitk <= 1 && a.N % 320 == 0 && ((conv && (t320 & 1)) || (!conv && a.epi == EPI_GEGLU && a.K >= 640 && (t320 & 2)) || (!conv && a.epi == EPI_GEGLU && a.K < 640 && a.K >= 320 && (t320 & 4)) ||
@@ -1651,45 +1589,37 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
         // instantiation the GEGLU launches use (its epilogue kind is a run-time argument): no new device code.  AE_GEMM_T320_XE=0 turns the rule off (A/B).
         static const int t320_xe = getenv("AE_GEMM_T320_XE") ? atoi(getenv("AE_GEMM_T320_XE")) : 1;
         const long t128x = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-        const bool xe_tail = t320_xe && !conv && a.xe == 2 && a.epi != EPI_GEGLU && (pp & 8) && fill >= 0.74 && fill < 0.85 &&
+        const bool xe_tail = t320_xe && !conv && a.xe == 2 && a.epi != EPI_GEGLU && fill >= 0.74 && fill < 0.85 &&
                              (double)t128x / (double)(((t128x + 511) / 512) * 512) <= 0.72;
         if (fill >= 0.85 || xe_tail) {
-            if (xe_tail) {
-                if constexpr (AMODE == A_DENSE) { rc = launch_kernel(gemm_kernel<192, 320, A_DENSE, 4, 2, true, 1, 2, false, 0, 3, 2>, (unsigned)t, 512, lds_aa(192, 320) + 2 * 320 * sizeof(float), stream, a, what); xe_done = true; }
-            } else
-            if (a.epi == EPI_GEGLU && (pp & 8)) {
-                if constexpr (AMODE == A_DENSE) {
-                    if (a.xe == 2) { rc = launch_kernel(gemm_kernel<192, 320, A_DENSE, 4, 2, true, 1, 2, false, 0, 3, 2>, (unsigned)t, 512, lds_aa(192, 320) + 2 * 320 * sizeof(float), stream, a, what); xe_done = true; }
-                    else rc = launch_kernel(gemm_kernel<192, 320, A_DENSE, 4, 2, true, 1, 2, false, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what);
-                }
-            }
-            else if (a.epi == EPI_GEGLU) rc = launch_kernel(gemm_kernel<192, 320, AMODE, 4, 2, true>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
-            else if (conv && (pp & 1) && !a.ups) {   // (the nearest-x2 gather: its per-piece address arithmetic measured 283 vs 273 us under the first form of the ping-pong loop; a second attempt with
-                                                     //  per-piece row / column offset tables — source pixel = virtual pixel >> 1 is not linear in the tap — measured 409 vs 330 us (hipcc kept the
-                                                     //  tables in scratch memory, profiles/r04_v23_ups_pp.txt).  Two launches per evaluation; they stay on the round-3 loop.)
-                if constexpr (AMODE == A_CONV3) {
-                    // flag 16: the slab form of the loop (WA = 4) where its preconditions hold — chunk-major K, stride 1, K range starting at tap 0
+            if constexpr (AMODE == A_DENSE) {
+                if (xe_tail || (a.epi == EPI_GEGLU && a.xe == 2)) { rc = launch_kernel(gemm_kernel<192, 320, A_DENSE, 4, 2, true, 1, 2, false, 0, 3, 2>, (unsigned)t, 512, lds_aa(192, 320) + 2 * 320 * sizeof(float), stream, a, what); xe_done = true; }
+                else if (a.epi == EPI_GEGLU) rc = launch_kernel(gemm_kernel<192, 320, A_DENSE, 4, 2, true, 1, 2, false, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what);
+                else rc = launch_kernel(gemm_kernel<192, 320, A_DENSE, 2, 4, true, 1, 2, false, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what);
+            } else {
+#ifdef AE_GEMM_ABLATE
+                if (lab_abl == 1) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 1>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
+                else if (lab_abl == 2) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 2>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
+                else if (lab_abl == 3) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 3>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
+                else if (lab_abl == 4) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 4>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
+                else if (lab_abl == 20) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, false>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);  // register-staged loader
+                else
+#endif
+                if (!a.ups) {   // (the nearest-x2 gather: its per-piece address arithmetic measured 283 vs 273 us under the first form of the ping-pong loop; a second attempt with
+                                //  per-piece row / column offset tables — source pixel = virtual pixel >> 1 is not linear in the tap — measured 409 vs 330 us (hipcc kept the
+                                //  tables in scratch memory, profiles/r04_v23_ups_pp.txt).  Two launches per evaluation; they stay on the round-3 loop.)
+                    // the slab form of the loop (WA = 4) where its preconditions hold — chunk-major K, stride 1, K range starting at tap 0
                     // (whole image rows per tile, 16-row fragments inside one image row, at most 200 slab rows)
-                    const bool slab = (pp & 16) && slab_ok;
-                    if (slab && cs_epi_ok) { rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, true, 0, 4>, (unsigned)t, 512, lds_slab, stream, a, what); cs_done = true; }
-                    else if (slab) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 4>, (unsigned)t, 512, lds_slab, stream, a, what);
+                    if (slab_ok && cs_epi_ok) { rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, true, 0, 4>, (unsigned)t, 512, lds_slab, stream, a, what); cs_done = true; }
+                    else if (slab_ok) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 4>, (unsigned)t, 512, lds_slab, stream, a, what);
                     else if (cs_epi_ok) { rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, true, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what); cs_done = true; }
                     else rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what);
+                } else if (cs_epi_ok) {
+                    rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, true>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
+                    cs_done = true;
                 }
-            } else if (!conv && (pp & 4)) {
-                if constexpr (AMODE == A_DENSE) rc = launch_kernel(gemm_kernel<192, 320, A_DENSE, 2, 4, true, 1, 2, false, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what);
-            } else if (cs_epi_ok && AMODE == A_CONV3) {
-                if constexpr (AMODE == A_CONV3) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, true>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
-                cs_done = true;
+                else rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
             }
-#ifdef AE_GEMM_ABLATE
-            else if (conv && lab_abl == 1) { if constexpr (AMODE == A_CONV3) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 1>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what); }
-            else if (conv && lab_abl == 2) { if constexpr (AMODE == A_CONV3) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 2>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what); }
-            else if (conv && lab_abl == 3) { if constexpr (AMODE == A_CONV3) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 3>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what); }
-            else if (conv && lab_abl == 4) { if constexpr (AMODE == A_CONV3) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 4>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what); }
-            else if (conv && lab_abl == 20) { if constexpr (AMODE == A_CONV3) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, false>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what); }  // register-staged loader
-#endif
-            else rc = launch_kernel(gemm_kernel<192, 320, AMODE, 2, 4, true>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
             done = true;
         }
     }
@@ -1707,24 +1637,22 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
     // launches and measured in the lab: convs 96.3 / 299.5 us against 94.8 / 293.0 for the two-blocks-per-CU 128x128 kernel, ff2 40.3 vs 43.4, qkv 44.0
     // vs 41.2 (profiles/r04_v17_pp256x128_experiment.txt): its 16-MFMA intervals are too short for the two barriers each costs.  Not kept.)
     static const int deep_pref = getenv("AE_GEMM_DEEP") ? atoi(getenv("AE_GEMM_DEEP")) : 1;
-    if (!done && deep_pref && !conv && glds && a.splitk <= 1 && a.epi != EPI_GEGLU && a.N % 128 == 0 && a.K >= 1280) {
-        const long t128 = (long)((a.M + 127) / 128) * (a.N / 128);
-        const long t192 = (long)((a.M + 191) / 192) * (a.N / 128);
-        if (t128 >= 128 && t128 <= 256) {
-            if (a.xe && AMODE == A_DENSE) {
-                if constexpr (AMODE == A_DENSE) {
-                    if (a.xe == 1) rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 3, false, 0, 0, 1>, (unsigned)t128, 512, lds_of(128, 128, 3), stream, a, what);
-                    else rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 3, false, 0, 0, 2>, (unsigned)t128, 512, lds_of(128, 128, 3), stream, a, what);
-                    xe_done = true;
-                }
-            } else
-            rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 3>, (unsigned)t128, 512, lds_of(128, 128, 3), stream, a, what);
-            done = true;
-        } else if (t128 > 256 && t192 >= 128 && t192 <= 256 && a.K >= 2560) {
-            // a taller tile that brings the grid down to one block per CU (SAM: M = 4096 x N = 1280 x K = 5120, 320 -> 220 blocks:
-            // 89 -> 80 us; at K = 1280 it is neutral, and a 256x128 tile for M = 4900 loses: 32.5 -> 38 us)
-            rc = launch_kernel(gemm_kernel<192, 128, AMODE, 4, 2, true, 1, 3>, (unsigned)t192, 512, lds_of(192, 128, 3), stream, a, what);
-            done = true;
+    if constexpr (AMODE == A_DENSE) {
+        if (!done && deep_pref && glds && a.splitk <= 1 && a.epi != EPI_GEGLU && a.N % 128 == 0 && a.K >= 1280) {
+            const long t128 = (long)((a.M + 127) / 128) * (a.N / 128);
+            const long t192 = (long)((a.M + 191) / 192) * (a.N / 128);
+            if (t128 >= 128 && t128 <= 256) {
+                if (a.xe == 1) rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 3, false, 0, 0, 1>, (unsigned)t128, 512, lds_of(128, 128, 3), stream, a, what);
+                else if (a.xe) rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 3, false, 0, 0, 2>, (unsigned)t128, 512, lds_of(128, 128, 3), stream, a, what);
+                else rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 3>, (unsigned)t128, 512, lds_of(128, 128, 3), stream, a, what);
+                xe_done = a.xe != 0;
+                done = true;
+            } else if (t128 > 256 && t192 >= 128 && t192 <= 256 && a.K >= 2560) {
+                // a taller tile that brings the grid down to one block per CU (SAM: M = 4096 x N = 1280 x K = 5120, 320 -> 220 blocks:
+                // 89 -> 80 us; at K = 1280 it is neutral, and a 256x128 tile for M = 4900 loses: 32.5 -> 38 us)
+                rc = launch_kernel(gemm_kernel<192, 128, A_DENSE, 4, 2, true, 1, 3>, (unsigned)t192, 512, lds_of(192, 128, 3), stream, a, what);
+                done = true;
+            }
         }
     }
     if (!done) {
@@ -1738,43 +1666,39 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
         // 64x64 grids up to three blocks per CU keep the ring too (its 48 KiB leave room for three resident blocks): training batch
         // M = 1024 x N = 1280 x K = 1280 (320 blocks) 31.7 -> ~20 us, training step 29.0 -> 28.0 ms.  AE_GEMM_DEEP64_MAX=256 restores round 1.
         static const int deep64_max = getenv("AE_GEMM_DEEP64_MAX") ? atoi(getenv("AE_GEMM_DEEP64_MAX")) : 768;
-        static const int conv_deep_l = getenv("AE_CONV_DEEP") ? atoi(getenv("AE_CONV_DEEP")) : 0;
-        // (a FOURTH stage — three tiles in flight, 128 KiB — measured the same on the 8x8-level convs: 41.9 vs 40.4 us; these launches are
+        // (a FOURTH ring stage — three tiles in flight, 128 KiB — measured the same on the 8x8-level convs: 41.9 vs 40.4 us; these launches are
         // not latency-bound by ring depth but by LDS bandwidth: 0.75 ds_read_b128 per MFMA x 8 cycles each against 16-cycle MFMAs)
-        if (conv && conv_deep_l && pick == 0 && glds && grid <= 256)
-            rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 3>, grid, 512, lds_of(128, 128, 3), stream, a, what);
-        else if (pick == 3) AE_LAUNCH(128, 160, 2, 2, 256);
-        else if (pick == 0 && w8 == 1) AE_LAUNCH(128, 128, 2, 4, 512);
-        else if (pick == 0 && wk_env && glds) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 2, 2, true, 2>, grid, 512, lds_of(128, 128, 2), stream, a, what);
-        else if (pick == 0 && w8 == 2 && cs_epi_ok && glds) {
-            if (wa & (conv ? 1 : 2)) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, true, 0, 1>, grid, 512, lds_wa(128, 128), stream, a, what);
-            else rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, true>, grid, 512, lds_of(128, 128, 2), stream, a, what);
-            cs_done = true;
-        } else if (pick == 0 && w8 == 2 && glds && (wa & (conv ? 1 : 2)) && kt_block >= 3) {
-            if (a.xe && AMODE == A_DENSE) {
-                if constexpr (AMODE == A_DENSE) {
-                    if (a.xe == 1) rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 2, false, 0, 1, 1>, grid, 512, lds_wa(128, 128), stream, a, what);
-                    else rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 2, false, 0, 1, 2>, grid, 512, lds_wa(128, 128), stream, a, what);
-                    xe_done = true;
-                }
-            } else
-            rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 0, 1>, grid, 512, lds_wa(128, 128), stream, a, what);
+        if (pick == 3) {   // convs only: a dense 128x160 pick was demoted to 128x64 above
+            if constexpr (AMODE == A_CONV3) AE_LAUNCH(128, 160, 2, 2, 256);
         }
 #ifdef AE_GEMM_ABLATE
-        else if (pick == 0 && w8 == 2 && glds && lab_abl == 1) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 1>, grid, 512, lds_of(128, 128, 2), stream, a, what);
-        else if (pick == 0 && w8 == 2 && glds && lab_abl == 2) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 2>, grid, 512, lds_of(128, 128, 2), stream, a, what);
-        else if (pick == 0 && w8 == 2 && glds && lab_abl == 3) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 3>, grid, 512, lds_of(128, 128, 2), stream, a, what);
-        else if (pick == 0 && w8 == 2 && glds && lab_abl == 4) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 4>, grid, 512, lds_of(128, 128, 2), stream, a, what);
+        else if (pick == 0 && glds && lab_abl == 1) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 1>, grid, 512, lds_of(128, 128, 2), stream, a, what);
+        else if (pick == 0 && glds && lab_abl == 2) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 2>, grid, 512, lds_of(128, 128, 2), stream, a, what);
+        else if (pick == 0 && glds && lab_abl == 3) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 3>, grid, 512, lds_of(128, 128, 2), stream, a, what);
+        else if (pick == 0 && glds && lab_abl == 4) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 4>, grid, 512, lds_of(128, 128, 2), stream, a, what);
 #endif
-        else if (pick == 0 && w8 == 2) AE_LAUNCH(128, 128, 4, 2, 512);
-        else if (pick == 0) AE_LAUNCH(128, 128, 2, 2, 256);
-        else if (pick == 1 && w8 && !conv) AE_LAUNCH(128, 64, 4, 2, 512);
-        else if (pick == 1) AE_LAUNCH(128, 64, 2, 2, 256);
-        else if (deep_pref && glds && !conv && a.splitk <= 1 && grid <= (unsigned)deep64_max && a.K >= 1280)
+        else if (pick == 0 && cs_epi_ok && glds) {
+            rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, true, 0, 1>, grid, 512, lds_wa(128, 128), stream, a, what);
+            cs_done = true;
+        } else if (pick == 0 && glds && (conv || kt_block >= 3)) {   // (a conv block has at least 8 K tiles: 9 per 64 input channels, split plans keep 8)
+            if constexpr (AMODE == A_DENSE) {
+                if (a.xe == 1) rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 2, false, 0, 1, 1>, grid, 512, lds_wa(128, 128), stream, a, what);
+                else if (a.xe) rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 2, false, 0, 1, 2>, grid, 512, lds_wa(128, 128), stream, a, what);
+                xe_done = a.xe != 0;
+            }
+            if (!a.xe) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 0, 1>, grid, 512, lds_wa(128, 128), stream, a, what);
+        }
+        else if (pick == 0) {
+            if constexpr (AMODE == A_DENSE) AE_LAUNCH(128, 128, 4, 2, 512);   // fewer than three K tiles, or the register-staged loader
+            else rc = launch_kernel(gemm_kernel<128, 128, A_CONV3, 4, 2, false>, grid, 512, lds_of(128, 128, 2), stream, a, what);   // register-staged loader
+        } else if (pick == 1) {
+            if constexpr (AMODE == A_DENSE) AE_LAUNCH(128, 64, 4, 2, 512);
+            else AE_LAUNCH(128, 64, 2, 2, 256);
+        } else if (deep_pref && glds && !conv && a.splitk <= 1 && grid <= (unsigned)deep64_max && a.K >= 1280) {
             // the same ring for small 64x64 grids (8x8 level, training batches): M = 768 x N = 1280 at K = 1280 / 2560 / 5120:
             // 23.3 -> 16.4, 37.4 -> 23.2, 67.3 -> 38.7 us; lower K thresholds and a fourth stage measured the same
-            rc = launch_kernel(gemm_kernel<64, 64, AMODE, 2, 2, true, 1, 3>, grid, 256, lds_of(64, 64, 3), stream, a, what);
-        else AE_LAUNCH(64, 64, 2, 2, 256);
+            if constexpr (AMODE == A_DENSE) rc = launch_kernel(gemm_kernel<64, 64, A_DENSE, 2, 2, true, 1, 3>, grid, 256, lds_of(64, 64, 3), stream, a, what);
+        } else AE_LAUNCH(64, 64, 2, 2, 256);
 #undef AE_LAUNCH
     }
     if (rc) return rc;
@@ -1785,7 +1709,7 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
         return AE_ERR_UNSUPPORTED;
     }
     if (g_plan_query) return 0;
-    if (a.splitk > 1 && !a.defer_reduce) {
+    if (a.splitk > 1) {
         long nb = ((long)a.M * a.N / 4 + 255) / 256;
         if (nb > 2048) nb = 2048;
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)nb), dim3(256), 0, stream, a);
@@ -1964,32 +1888,6 @@ extern "C" long ae_conv3x3_workspace_floats(int B, int H, int W, int Cin, int Co
     const long M = (long)B * Ho * Wo;
     const int s = make_plan((int)M, Cout, 9 * CinPad, true).splitk;
     return s > 1 ? (long)s * M * Cout : 0;
-}
-
-// The split-K plan of ae_conv3x3_bf16 (stride 1, no upsampling) stopped at its fp32 partials: workspace [splitk][B*H*W][Cout] holds the K ranges' raw products
-// (no bias); *splitk_out = the number of ranges, 0 when the plan does not split this shape (nothing is launched then: call ae_conv3x3_bf16).
-extern "C" int ae_conv3x3_partials_bf16(const void* x, const void* w, int B, int H, int W, int Cin, int Cout, float* workspace, int k_order, int* splitk_out, void* stream) {
-    AE_REQUIRE(x && w && workspace && splitk_out, "ae_conv3x3_partials_bf16: null pointer");
-    AE_REQUIRE(k_order == 0 || k_order == 1, "ae_conv3x3_partials_bf16: k_order must be 0 (tap, channel) or 1 (64-channel chunk, tap, channel)");
-    AE_REQUIRE(k_order == 0 || Cin % 64 == 0, "ae_conv3x3_partials_bf16: the chunk-major K order needs Cin %% 64 == 0 (Cin=%d)", Cin);
-    AE_REQUIRE(B > 0 && H > 0 && W > 0 && Cin % 8 == 0 && Cout % 4 == 0, "ae_conv3x3_partials_bf16: bad shape B=%d H=%d W=%d Cin=%d Cout=%d", B, H, W, Cin, Cout);
-    AE_REQUIRE(aligned16(x) && aligned16(w) && aligned16(workspace), "ae_conv3x3_partials_bf16: pointers must be 16-byte aligned");
-    GemmArgs a{};
-    a.A = (const bf16_t*)x; a.W = (const bf16_t*)w; a.C = nullptr;
-    const int CinPad = (Cin + BK - 1) / BK * BK;
-    a.M = B * H * W; a.N = Cout; a.K = 9 * CinPad; a.Ksplit = a.K;
-    a.ldw = 9L * CinPad; a.ldc = Cout; a.ldr = Cout; a.ldav = Cout;
-    a.epi = EPI_NONE; a.rows_per_batch = H * W;
-    a.H = H; a.Wd = W; a.Cin = Cin; a.CinPad = CinPad; a.Ho = H; a.Wo = W; a.stride = 1; a.ups = 0;
-    a.a_bytes = (unsigned)((long)B * H * W * Cin * 2); a.w_bytes = (unsigned)((long)Cout * 9 * CinPad * 2);
-    AE_REQUIRE((long)B * H * W * Cin * 2 < (1L << 31) && (long)Cout * 9 * CinPad * 2 < (1L << 31), "ae_conv3x3_partials_bf16: operands must be smaller than 2 GiB");
-    a.splitk = make_plan(a.M, a.N, a.K, true).splitk;
-    *splitk_out = a.splitk > 1 ? a.splitk : 0;
-    if (a.splitk <= 1) return AE_OK;
-    a.partial = workspace;
-    a.kmajor = k_order;
-    a.defer_reduce = 1;
-    return launch<A_CONV3>(a, (hipStream_t)stream);
 }
 
 extern "C" int ae_conv3x3_bf16(const void* x, const void* w, const float* bias, const float* addvec, long addvec_ld,

@@ -1,4 +1,4 @@
-// Helpers of the HAND-PLACED kernels (one wave per SIMD, csrc/ff_fused.hip, csrc/xattn_fused.hip): every MFMA is an asm statement — program order is kept and
+// Helpers of the HAND-PLACED kernels (one wave per SIMD, csrc/ff_fused.hip): every MFMA is an asm statement — program order is kept and
 // the register file of each accumulator is the constraint's ("v": VGPR, "a": the accumulator half) — followed by its slice of VALU work and a scheduling barrier.
 // hipcc pads nothing around asm MFMAs and keeps no books for them: operands written by VALU must be a phase old when an MFMA reads them, results are read by
 // VALU a phase later or after explicit nops, and operand fragments stay live (`hp_keep`) until two further MFMAs have been issued (the MFMA-source rule of

@@ -280,110 +280,6 @@ def ff_fused(x, gamma, beta, eps, w1, b1, w2img, b2, residual=None, out=None, w3
     return out
 
 
-# --------------------------------------------------------------------------- fused cross-attention half (csrc/xattn_fused.hip)
-def pack_xattn_wq(wq):
-    """to_q weight [320, 320] (8 heads of 40) -> the Wq_h LDS images of `ae_xattn_fused_bf16`: bf16 [8, 48, 320], rows 40 .. 47 of a head zero, the 16-byte pieces of a
-    row XOR-swizzled inside groups of eight (piece c of image row i at position (c & ~7) | ((c ^ (i >> 1)) & 7): the row-panel kernel's image).  Once per weight version."""
-    assert tuple(wq.shape) == (320, 320)
-    dev = wq.device
-    img = torch.zeros(8, 48, 40, 8, dtype=torch.float32, device=dev)                       # [head][row][piece][8 elements]
-    img[:, :40] = wq.detach().float().reshape(8, 40, 40, 8)
-    i = torch.arange(48, device=dev)[:, None]
-    c = torch.arange(40, device=dev)[None, :]
-    pos = (c & ~7) | ((c ^ (i >> 1)) & 7)                                                   # [48, 40]: where piece c of row i is stored
-    out = torch.zeros_like(img)
-    out.scatter_(2, pos[None, :, :, None].expand(8, 48, 40, 8), img)
-    return out.reshape(8, 48, 320).to(BF16).contiguous()
-
-
-def pack_xattn_wo(wo):
-    """to_out weight [320, 320 = 8 heads x 40] -> bf16 [4 head pairs, 320, 112]: image row i holds output column 32 (i >> 5) + 8 ((i & 15) >> 2) + 4 ((i & 31) >> 4) + (i & 3);
-    its bytes are three K steps of 64 B (+ 32 B pad, row stride 224 B: conflict-free fragment reads); K step t, lane group g, element e is d slot 16 (q % 3) + 4 g + (e & 3) of head
-    2 pair + (q >= 3), q = 2 t + (e >> 2) — the order the attention output of two heads sits in the result registers — and zero for slots 40 .. 47."""
-    assert tuple(wo.shape) == (320, 320)
-    dev = wo.device
-    i = torch.arange(320, device=dev)
-    i5 = i & 31
-    col = 32 * (i >> 5) + 8 * ((i5 & 15) >> 2) + 4 * (i5 >> 4) + (i5 & 3)
-    s = torch.arange(96, device=dev)
-    t, g, e = s >> 5, (s >> 3) & 3, s & 7
-    q6 = 2 * t + (e >> 2)
-    dslot = 16 * (q6 % 3) + 4 * g + (e & 3)
-    hloc = (q6 >= 3).long()
-    wf = torch.cat([wo.detach().float()[col].reshape(320, 8, 40), torch.zeros(320, 8, 8, device=dev)], dim=2)   # [row, head, 48 slots]
-    out = torch.zeros(4, 320, 112, dtype=torch.float32, device=dev)
-    for pr in range(4):
-        out[pr, :, :96] = wf[:, 2 * pr + hloc, dslot]
-    return out.to(BF16).contiguous()
-
-
-def pack_xattn_kv(kv, kv_ip, B, Nk, T):
-    """K | V of a cross-attention layer's context [B * Nk, 640] (and of its T-token expert segment [B * T, 640] or None) -> the per-(sample, head) LDS images of
-    `ae_xattn_fused_bf16`, bf16 [B, 8, 14848]: K image [96 key rows (80 text, 16 expert)][80] (64 d slots in the order the q results sit in registers + 16 pad: 160-byte rows)
-    then V^T image [48 d rows][144] (4 K steps of 32 key slots in the logits' order + 16 pad; row 40 = ones: the softmax denominator) + 256 pad.  Step-invariant: once per edit."""
-    assert 64 < Nk <= 80 and 0 <= T <= 16
-    dev = kv.device
-    kvb = kv.reshape(B, Nk, 640).float()
-    Kt = torch.zeros(B, 96, 320, device=dev)
-    Vt = torch.zeros(B, 96, 320, device=dev)
-    Kt[:, :Nk], Vt[:, :Nk] = kvb[:, :, :320], kvb[:, :, 320:]
-    if kv_ip is not None and T > 0:
-        ipb = kv_ip.reshape(B, T, 640).float()
-        Kt[:, 80:80 + T], Vt[:, 80:80 + T] = ipb[:, :, :320], ipb[:, :, 320:]
-    s = torch.arange(64, device=dev)
-    t, g, e = s >> 5, (s >> 3) & 3, s & 7
-    dslot = 16 * (2 * t + (e >> 2)) + 4 * g + (e & 3)                                       # 0 .. 63 (>= 40: zero)
-    Kh = torch.cat([Kt.reshape(B, 96, 8, 40).permute(0, 2, 1, 3), torch.zeros(B, 8, 96, 24, device=dev)], dim=3)
-    Kimg = torch.zeros(B, 8, 96, 80, device=dev)
-    Kimg[..., :64] = Kh[..., dslot]
-    s = torch.arange(128, device=dev)
-    t, g, e = s >> 5, (s >> 3) & 3, s & 7
-    j = e >> 2
-    key = torch.where(t < 3, 16 * (2 * t + j) + 4 * g + (e & 3), 80 + 4 * g + (e & 3))      # text K steps: key index; expert K step: rows 80 ..
-    ok = torch.where(t < 3, key < 80, j == 0)
-    Vh = Vt.reshape(B, 96, 8, 40).permute(0, 2, 3, 1)                                       # [B, 8, 40, 96]
-    Vimg = torch.zeros(B, 8, 48, 144, device=dev)
-    Vimg[:, :, :40, :128] = Vh[..., key.clamp(max=95)] * ok.float()
-    Vimg[:, :, 40, :128] = 1.0
-    out = torch.zeros(B, 8, 14848, device=dev)
-    out[..., :7680] = Kimg.reshape(B, 8, 7680)
-    out[..., 7680:7680 + 6912] = Vimg.reshape(B, 8, 6912)
-    return out.to(BF16).contiguous()
-
-
-def xattn_fused_ok(M, C, heads, head_dim, rows_per_sample, Nk, T):
-    """True where `xattn_fused` covers the cross-attention half of a transformer block (never while the training tape records)."""
-    return not (_TAPE is not None and _TAPE.active) and bool(lib.ae_xattn_fused_supported(M, C, heads, head_dim, rows_per_sample, Nk, T))
-
-
-def xattn_fused(x, gamma, beta, eps, wq_img, kv_img, gate, wo_img, bo, rows_per_sample, Nk, T, scale, out=None):
-    """out = to_out(Attn(to_q(LayerNorm(x)), K, V) + gate_b Attn(., K_ip, V_ip)) + x in ONE launch (attention.py:273 `x = attn2(norm2(x), context) + x`): x [M, 320] bf16
-    rows, (wq_img, wo_img, kv_img) = `pack_xattn_wq / _wo / _kv`, gate fp32 [B] or None.  Callers ask `xattn_fused_ok` first."""
-    _chk(x, BF16, "xattn_fused.x", 2)
-    _chk(wq_img, BF16, "xattn_fused.wq_img", 3)
-    _chk(wo_img, BF16, "xattn_fused.wo_img", 3)
-    _chk(kv_img, BF16, "xattn_fused.kv_img", 3)
-    _chk(gamma, torch.float32, "xattn_fused.gamma", 1)
-    _chk(beta, torch.float32, "xattn_fused.beta", 1)
-    M, C = x.shape
-    B = M // rows_per_sample
-    if tuple(wq_img.shape) != (8, 48, 320) or tuple(wo_img.shape) != (4, 320, 112) or tuple(kv_img.shape) != (B, 8, 14848) or not (wq_img.is_contiguous() and wo_img.is_contiguous()
-                                                                                                                                    and kv_img.is_contiguous()) or x.stride(1) != 1:
-        raise ValueError(f"xattn_fused: x {tuple(x.shape)}, images {tuple(wq_img.shape)} / {tuple(wo_img.shape)} / {tuple(kv_img.shape)} do not fit together")
-    if gate is not None:
-        _chk(gate, torch.float32, "xattn_fused.gate", 1)
-        if gate.numel() != B:
-            raise ValueError("xattn_fused: one gate per sample")
-    if bo is not None:
-        _chk(bo, torch.float32, "xattn_fused.bo", 1)
-    if out is None:
-        out = torch.empty(M, C, dtype=BF16, device=x.device)
-    _chk(out, BF16, "xattn_fused.out", 2)
-    check(lib.ae_xattn_fused_bf16(_p(x), x.stride(0), _p(gamma), _p(beta), float(eps), _p(wq_img), _p(kv_img), _p(gate), _p(wo_img), _p(bo), _p(out), out.stride(0), M,
-                                  rows_per_sample, Nk, T, float(scale), _s()), "ae_xattn_fused_bf16")
-    return out
-
-
 # --------------------------------------------------------------------------- GEMM / conv
 def colstats_buffer(M, N, device):
     """fp32 [ceil(M/32), N, 2]: per-channel (sum, sum of squares) over each 32-row slab of a bf16 [M, N] activation — filled by the kernel
@@ -620,65 +516,8 @@ def conv3x3(x, w, bias, B, H, W, addvec=None, residual=None, stride=1, upsample2
     return out, Ho, Wo
 
 
-# Opt-in (AE_GN_SPLITK=1): ResBlock conv1 -> GroupNorm at the 16x16 / 8x8 levels through the split-K fold below.  Built, bit-identical, one launch fewer per ResBlock (12 per UNet
-# evaluation) — and measured SLOWER in the graph: 12.345 -> 12.379 ms per evaluation (256-thread blocks) / 12.374 (1024-thread lab form), three alternating triples on one box
-# (profiles/r06_v30_gn_splitk_ab.txt): the reduce launch streams the 31-63 MB of partials with the whole chip, the slab GroupNorm behind it reads 8 MB from L2; the folding
-# GroupNorm reads the partials with 384 blocks in 160-byte row segments.  Default off.
-_GN_SPLITK = os.environ.get("AE_GN_SPLITK", "0") == "1"
-
-
-def conv3x3_gn_splitk_ok(B, H, W, Cin, Cout, groups=32):
-    """True where `conv3x3_partials` + `groupnorm_splitk` replace conv3x3 (+ its split-K reduce launch) + groupnorm: a stride-1 conv whose plan cuts K (the 16x16 /
-    8x8 UNet levels at batch 12) feeding a GroupNorm that runs the one-launch slab form (maps up to 256 positions).  Not under the training tape."""
-    if not _GN_SPLITK or (_TAPE is not None and _TAPE.active) or H * W > 256 or Cin % 8 or Cout % 8:
-        return False
-    nws = lib.ae_conv3x3_workspace_floats(B, H, W, Cin, Cout, 1, 0)
-    if nws <= 0:
-        return False
-    return bool(lib.ae_groupnorm_splitk_supported(B, H * W, Cout, groups, int(nws // (B * H * W * Cout))))
-
-
-def conv3x3_partials(x, w, B, H, W, k_order=0):
-    """The split-K plan of `conv3x3` (stride 1) stopped at its fp32 partials: returns (partials [splitk, B*H*W, Cout] fp32, splitk); the bias, the per-sample
-    vector and the rounding belong to the consumer (`groupnorm_splitk`).  Raises where the plan does not split (ask `conv3x3_gn_splitk_ok` first)."""
-    _no_tape("conv3x3_partials")
-    _chk(x, BF16, "conv3x3_partials.x", 2)
-    _chk(w, BF16, "conv3x3_partials.w", 2)
-    Cin, Cout = x.shape[1], w.shape[0]
-    if x.shape[0] != B * H * W or not x.is_contiguous() or w.shape[1] != 9 * ((Cin + 63) // 64 * 64):
-        raise ValueError(f"conv3x3_partials: x [B*H*W, Cin] contiguous and w packed [Cout, 9*CinPad] expected, got {tuple(x.shape)} / {tuple(w.shape)}")
-    nws = lib.ae_conv3x3_workspace_floats(B, H, W, Cin, Cout, 1, 0)
-    if nws <= 0:
-        raise ValueError(f"conv3x3_partials: the plan of [{B * H * W}, {Cin}] -> {Cout} does not cut K")
-    ws = torch.empty(nws, dtype=torch.float32, device=x.device)
-    sk = ctypes.c_int(0)
-    check(lib.ae_conv3x3_partials_bf16(_p(x), _p(w), B, H, W, Cin, Cout, _p(ws), int(k_order), ctypes.byref(sk), _s()), "ae_conv3x3_partials_bf16")
-    if sk.value < 2 or sk.value * B * H * W * Cout != nws:
-        raise RuntimeError(f"conv3x3_partials: plan mismatch (splitk {sk.value}, workspace {nws})")
-    return ws.view(sk.value, B * H * W, Cout), sk.value
-
-
-def groupnorm_splitk(partials, bias, addvec, gamma, beta, B, HW, eps, silu=False, groups=32, out=None):
-    """GroupNorm(+SiLU) of x = bf16(sum_s partials[s] + bias + addvec[b]) without x ever being written (`ae_groupnorm_splitk_nhwc_bf16`): bit-identical to
-    `conv3x3(..., bias, addvec)` followed by `groupnorm` on the small-map path.  partials: `conv3x3_partials`; bias fp32 [C] or None; addvec fp32 [B, C]
-    (rows may be strided) or None."""
-    _no_tape("groupnorm_splitk")
-    sk, M, C = partials.shape
-    if partials.dtype != torch.float32 or not partials.is_contiguous() or M != B * HW:
-        raise ValueError(f"groupnorm_splitk: partials must be contiguous fp32 [splitk, B*HW, C], got {tuple(partials.shape)} {partials.dtype}")
-    if addvec is not None and (addvec.dtype != torch.float32 or tuple(addvec.shape) != (B, C) or addvec.stride(1) != 1):
-        raise ValueError(f"groupnorm_splitk: addvec must be fp32 [B, C] with unit column stride, got {tuple(addvec.shape)} {addvec.dtype}")
-    if out is None:
-        out = torch.empty(M, C, dtype=BF16, device=partials.device)
-    check(lib.ae_groupnorm_splitk_nhwc_bf16(_p(partials), sk, _p(bias), _p(addvec), addvec.stride(0) if addvec is not None else 0, _p(gamma), _p(beta), _p(out),
-                                            B, HW, C, groups, eps, 1 if silu else 0, _s()), "ae_groupnorm_splitk_nhwc_bf16")
-    return out
-
-
 # --------------------------------------------------------------------------- norms
 _GN_COUNTERS = {}
-_GN_LAB_SKIP = os.environ.get("AE_GN_LAB_SKIP_FINALIZE") == "1"   # see csrc/norm.hip: upper bound of removing the finalize launch
-_GN_LAB_WS = {}
 
 
 _GN_TAIL = os.environ.get("AE_GN_TAIL") == "1"   # the last-block finalize is a measured loss on MI355X (DESIGN.md §7a): opt-in only
@@ -717,15 +556,7 @@ def groupnorm(x, gamma, beta, B, HW, eps, silu=False, groups=32, x2=None, out=No
             if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (B * HW // 32, c, 2) or not t.is_contiguous() or HW % 32):
                 raise ValueError(f"groupnorm: {n} must be a contiguous fp32 [{B * HW // 32}, {c}, 2] buffer (HW % 32 == 0), got {tuple(t.shape)}")
     nws = int(lib.ae_groupnorm_workspace_floats(B, HW, C, groups))
-    if _GN_LAB_SKIP and colstats is not None:   # lab (timing only, wrong results): the finalize launch is left out, the apply reads an all-zero coefficient buffer
-        ws = _GN_LAB_WS.get((nws, x.device))
-        if ws is None:
-            ws = _GN_LAB_WS[(nws, x.device)] = torch.zeros(nws, dtype=torch.float32, device=x.device)
-            rpc = int(lib.ae_groupnorm_rows_per_chunk(HW, C))
-            off = ((B * ((HW + rpc - 1) // rpc) * groups * 2 + 3) // 4) * 4
-            ws[off:off + B * 2 * C].view(B, 2, C)[:, 0] = 1.0   # scale 1, shift 0: the data keeps flowing (all-zero activations would run the chip at zero-data clocks)
-    else:
-        ws = torch.empty(nws, dtype=torch.float32, device=x.device)
+    ws = torch.empty(nws, dtype=torch.float32, device=x.device)
     check(lib.ae_groupnorm_nhwc_bf16(_p(x), _p(x2), C1, _p(gamma), _p(beta), _p(out), B, HW, C, groups, eps,
                                      1 if silu else 0, _p(ws), _p(_gn_counters(x.device, B)), _p(stat_out), _p(colstats), _p(colstats2), _s()),
           "ae_groupnorm_nhwc_bf16")
@@ -2156,8 +1987,8 @@ def _tile_label(M, N, conv=False, K=0, geglu=False, dma_ok=True, xe2=False):
         t128 = -(-M // 128) * -(-N // 128)
         if xe2 and not conv and not geglu and 0.74 <= fill < 0.85 and t128 / (-(-t128 // 512) * 512) <= 0.72 and os.environ.get("AE_GEMM_T320_XE", "1") != "0":
             return "192x320"   # round 5: a LayerNorm-fold launch whose 128x128 grid leaves a bad tail (qkv of the 16x16 level)
-    if conv and _conv_splitk(M, N, K) > 1:  # small grids: one block per CU under the three-stage ring (a different kernel symbol)
-        return "128x128,ring3,splitK" if dma_ok and _CONV_DEEP and -(-M // 128) * -(-N // 128) * _conv_splitk(M, N, K) <= 256 else "128x128,splitK"
+    if conv and _conv_splitk(M, N, K) > 1:
+        return "128x128,splitK"
     if conv and N % 160 == 0 and N % 128 != 0 and -(-M // 128) * (N // 160) >= 256:
         return "128x160"
     if not conv and not geglu and dma_ok and N % 128 == 0 and K >= 1280 and 128 <= -(-M // 128) * (N // 128) <= 256:
@@ -2173,9 +2004,6 @@ def _tile_label(M, N, conv=False, K=0, geglu=False, dma_ok=True, xe2=False):
     if not conv and dma_ok and K >= 1280 and -(-M // 64) * -(-N // 64) <= 768:
         return "64x64,ring3"
     return "64x64"
-
-
-_CONV_DEEP = os.environ.get("AE_CONV_DEEP", "0") != "0"  # mirror of the library's knob (small conv grids under the three-stage ring; default off since round 3)
 
 
 def _conv_t320_split(M, N, K):
@@ -2201,7 +2029,7 @@ def _conv_splitk(M, N, K):
     if kt < 32 or picked_big or is160:
         return 1
     if -(-N // 128) * 128 / N <= 1.10 and t128 < 256:
-        s_ = min((256 // t128) if (t128 <= 128 and _CONV_DEEP) else -(-480 // t128), int(os.environ.get("AE_CONV_SPLIT_MAX", "8")), kt // 8)
+        s_ = min(-(-480 // t128), int(os.environ.get("AE_CONV_SPLIT_MAX", "8")), kt // 8)
         return s_ if s_ >= 2 else 1
     return 1
 
@@ -2292,8 +2120,6 @@ def _up2_label(_r, x, w4, bias, B, H, W, **_):
 
 
 conv3x3_up2 = _wrap_profiled(conv3x3_up2, _up2_label)
-xattn_fused = _wrap_profiled(xattn_fused, lambda _r, x, gamma, beta, eps, wq_img, kv_img, gate, wo_img, bo, rows_per_sample, Nk, T, scale, out=None: (
-    f"xattn_fused_kernel<C=320>|M={x.shape[0]} Nk={Nk}+{T}", 2.0 * x.shape[0] * 320 * (2 * 320 + 2 * (Nk + T)), float(2 * (3 * x.numel() + wq_img.numel() + wo_img.numel() + kv_img.numel()))))
 ff_fused = _wrap_profiled(ff_fused, lambda _r, x, gamma, beta, eps, w1, b1, w2img, b2, residual=None, out=None, w3=None, b3=None, residual3=None, colstats=None: (
     f"ff_fused_kernel<C=320{',proj_out' if w3 is not None else ''}>|M={x.shape[0]} H={w1.shape[0] // 2}",
     2.0 * x.shape[0] * x.shape[1] * (3 * (w1.shape[0] // 2) + (x.shape[1] if w3 is not None else 0)),
@@ -2304,11 +2130,6 @@ _gemm_ln_launch = _wrap_profiled(_gemm_ln_launch, _gemm_ln_label)
 gemm = _wrap_profiled(gemm, _gemm_label)
 attention_fp8 = _wrap_profiled(attention_fp8, _attn8_label)
 conv3x3 = _wrap_profiled(conv3x3, _conv_label)
-conv3x3_partials = _wrap_profiled(conv3x3_partials, lambda _r, x, w, B, H, W, k_order=0: (
-    f"gemm_kernel<{_tile_label(x.shape[0], w.shape[0], True, 9 * (-(-x.shape[1] // 64) * 64), False, x.shape[1] % 64 == 0)},conv3x3>|M={x.shape[0]} Cin={x.shape[1]} Cout={w.shape[0]} s1 partials",
-    2.0 * x.shape[0] * w.shape[0] * 9 * x.shape[1], float(2 * (x.numel() + 9 * x.shape[1] * w.shape[0]) + 2 * x.shape[0] * w.shape[0]), 1))
-groupnorm_splitk = _wrap_profiled(groupnorm_splitk, lambda _r, partials, *a, **k: (
-    f"groupnorm(splitK fold)|rows={_r.shape[0]} C={_r.shape[1]}", 0.0, 2.0 * _r.numel() * 2, 1))
 attention = _wrap_profiled(attention, _attn_label)
 groupnorm = _wrap_profiled(groupnorm, _gn_label)
 layernorm = _wrap_profiled(layernorm, _ln_label)

@@ -97,24 +97,6 @@ int ae_ff_fused_bf16(const void* X, long ldx, const float* ln_gamma, const float
                      const void* W2img, const float* b2, const void* residual, long ldr, const void* W3, long ldw3, const float* b3,
                      const void* residual3, long ldr3, float* colstats, void* Y, long ldy, int M, int C, int H, void* stream);
 
-/* Fused cross-attention half of a BasicTransformerBlock at the 64x64 UNet level (round 6; ldm/modules/attention.py:273 `x = self.attn2(self.norm2(x), context=context) + x`:
- * norm2, CrossAttention.forward :163-194 (to_q, softmax(QK^T)V over the text keys, to_out) and the residual; with AnySD's decoupled expert segment) — ONE launch
- * instead of three (LayerNorm-fold q projection, short-K/V attention, to_out); q, logits, probabilities and the attention output stay in registers:
- *   Y[M,320] = ( softmax(q K^T) V + gate_b softmax(q K_ip^T) V_ip ) Wo^T + bo + X,    q = LayerNorm(X; gamma, beta, eps) Wq^T,   8 heads of 40, logits scaled by `scale`.
- *   X, Y bf16 rows (16-byte aligned, strides % 8 == 0, Y != X); rows_per_sample = tokens per sample (a multiple of 128; M a multiple of it);
- *   Wq_img bf16 [8][48][320], Wo_img bf16 [4][320][112], KV_img bf16 [B][8][ae_xattn_fused_kv_bytes() / 2]: the weights and the sample's K | V (Nk text keys, 64 < Nk <= 80,
- *   T <= 16 expert keys) as the kernel's LDS images (layouts: header of csrc/xattn_fused.hip; ops.pack_xattn_wq / _wo / _kv build them — the K | V images once per edit: they are
- *   step-invariant); gate fp32 [B] or NULL (no expert segment: T = 0); bo fp32 [320] or NULL.
- * ae_xattn_fused_supported(M, C, heads, head_dim, rows_per_sample, Nk, T): 1 where the kernel covers the shape (C == 320, 8 heads of 40, M >= 256 * 128 rows: one
- * 128-row block per CU and round) AND AE_XATTN_FUSED=1 is set, 0 otherwise — callers then run ae_gemm_ln_bf16 + ae_attn_fwd_bf16 + ae_gemm_ln_bf16.  Opt-in: results
- * match the three launches (tests/test_hip_ops.py), the launch is slower than they are at UNet batch 12 (profiles/r06_xattn_fused_notes.txt).                          */
-int ae_xattn_fused_supported(int M, int C, int heads, int head_dim, int rows_per_sample, int Nk, int T);
-/* shape envelope alone (what ae_xattn_fused_bf16 requires); ae_xattn_fused_supported adds the AE_XATTN_FUSED switch and the one-block-per-CU plan rule */
-int ae_xattn_fused_covers(int M, int C, int heads, int head_dim, int rows_per_sample, int Nk, int T);
-long ae_xattn_fused_kv_bytes(void);
-int ae_xattn_fused_bf16(const void* X, long ldx, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* Wq_img, const void* KV_img, const float* gate,
-                        const void* Wo_img, const float* bo, void* Y, long ldy, int M, int rows_per_sample, int Nk, int T, float scale, void* stream);
-
 /* 3x3 convolution, padding 1, as implicit GEMM (ResBlock in/out convs openaimodel.py:200-231, stem :536-542, head :726-730,
  * Downsample stride 2 :157-159, Upsample nearest-x2 + conv :108-118 via upsample2x=1).
  *   x [B,H,W,Cin] bf16 channels-last (Cin % 8 == 0), w [Cout, 9*CinPad] bf16 packed (ky,kx,cin) with CinPad = Cin
@@ -125,10 +107,6 @@ int ae_xattn_fused_bf16(const void* X, long ldx, const float* ln_gamma, const fl
  *   k_order: 0 = w packed (ky,kx,cin) as above; 1 = w packed (cin / 64, ky, kx, cin % 64) — the nine taps of a 64-channel chunk
  *   in consecutive K tiles, so a block re-reads its activation window from L2 (Cin % 64 == 0, no upsampling); same result.   */
 long ae_conv3x3_workspace_floats(int B, int H, int W, int Cin, int Cout, int stride, int upsample2x);
-/* The split-K plan of ae_conv3x3_bf16 (stride 1, no upsampling) stopped at its fp32 partials: workspace (ae_conv3x3_workspace_floats elements) receives the raw
- * products of the K ranges, [splitk][B*H*W][Cout]; *splitk_out = their number, or 0 when the plan does not cut K for this shape (nothing is launched: call
- * ae_conv3x3_bf16).  The bias, the time-embedding vector and the rounding are the consumer's: ae_groupnorm_splitk_nhwc_bf16 (openaimodel.py:262-272).            */
-int ae_conv3x3_partials_bf16(const void* x, const void* w, int B, int H, int W, int Cin, int Cout, float* workspace, int k_order, int* splitk_out, void* stream);
 int ae_conv3x3_bf16(const void* x, const void* w, const float* bias, const float* addvec, long addvec_ld, const void* residual,
                     void* y, int B, int H, int W, int Cin, int Cout, int stride, int upsample2x, int out_f32, float* workspace,
                     float* colstats /* as for ae_gemm_bf16 (M = B*Ho*Wo, N = Cout); NULL = none */, int k_order, void* stream);
@@ -151,19 +129,12 @@ int ae_conv3x3_up2_bf16(const void* x, const void* w4, const float* bias, void* 
  * stream: the last partial-sum block of each sample then runs the statistics fold itself (two launches instead of three, same
  * fixed summation order, bit-identical result).  NULL keeps the stand-alone finalize launch.  The tail is OFF unless AE_GN_TAIL=1:
  * measured 3 ms per UNet step slower on MI355X (every block's device-scope release is an L2 write-back).
- * stat_out: optional fp32 [B][groups][2] (mean, rstd) kept for ae_groupnorm_bwd_nhwc_bf16.                                      */
-int ae_groupnorm_rows_per_chunk(int HW, int C);
-long ae_groupnorm_workspace_floats(int B, int HW, int C, int groups);
-/* GroupNorm(+SiLU) of x = bf16(sum_s partial[s] + bias + addvec[b]) where x is never written: ResBlock's `h = in_conv(h) + emb_out; h = out_norm(h); h = SiLU(h)`
- * (openaimodel.py:262-272) at the 16x16 / 8x8 levels, whose convs cut K.  partial: ae_conv3x3_partials_bf16's [splitk][B*HW][C] fp32; bias [C], addvec [B, >= C]
- * (row stride addvec_ld) fp32 or NULL.  Same arithmetic as ae_conv3x3_bf16's reduce launch followed by ae_groupnorm_nhwc_bf16 (one-launch slab form), bit for bit;
- * one launch and one round trip of the activation less.  ae_groupnorm_splitk_supported: maps up to 256 positions, 2..8 K ranges.                                */
-int ae_groupnorm_splitk_supported(int B, int HW, int C, int groups, int splitk);
-int ae_groupnorm_splitk_nhwc_bf16(const float* partial, int splitk, const float* bias, const float* addvec, long addvec_ld, const float* gamma, const float* beta,
-                                  void* y, int B, int HW, int C, int groups, float eps, int act, void* stream);
+ * stat_out: optional fp32 [B][groups][2] (mean, rstd) kept for ae_groupnorm_bwd_nhwc_bf16.
  * colstats / colstats2: optional per-channel slab statistics of x / x2 as written by the kernels that PRODUCED them (the `colstats`
  * output of ae_gemm_bf16 / ae_ln_gemm_bf16 / ae_conv3x3_bf16: [B*HW/32][C1][2] and [B*HW/32][C-C1][2]; HW % 32 == 0).  With them the
  * statistics pass over the activation is skipped: one block per (sample, group) folds the slab sums, then the apply launch runs.    */
+int ae_groupnorm_rows_per_chunk(int HW, int C);
+long ae_groupnorm_workspace_floats(int B, int HW, int C, int groups);
 int ae_groupnorm_nhwc_bf16(const void* x, const void* x2, int C1, const float* gamma, const float* beta, void* y, int B, int HW,
                            int C, int groups, float eps, int act, float* workspace, int* counters, float* stat_out,
                            const float* colstats, const float* colstats2, void* stream);

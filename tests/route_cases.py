@@ -6,9 +6,8 @@ kernels it launched and checks the output element by element (see that script's 
 LEDGER: one row per kernel instantiation of the two files in the default build, keyed by the template-argument tuple as c++filt prints it
 (`gemm_kernel<192, 320, 1, 2, 4, true, 1, 2, false, 0, 4, 0>`: BM, BN, AMODE (0 dense, 1 conv), WAVES_M, WAVES_N, GLDS, WAVES_K, STAGES,
 CS, LAB, WA, XE; `attn_fast_kernel<D, OCC, SEG2, ABL, BIAS, QG, VSPLIT, SKV, NWV, SKT>`; `attn_pipe_kernel<D, KT, PV16>`).  Each row is
-  ("default", [case ids])   reached with no AE_* variable set, by every case listed;
-  ("knob", "AE_X=v")        reached only under that tuning knob;
-  ("unreachable", "why")    compiled, never launched (the launcher line that excludes it).
+  ("default", [case ids])   reached with no AE_* variable set, by every case listed.
+The default build compiles nothing that no case reaches.
 """
 
 # --------------------------------------------------------------------------------------------------- cases
@@ -179,59 +178,34 @@ def _af(*a):
     return "attn_fast_kernel<" + ", ".join(str(x).lower() for x in a) + ">"
 
 
-_DENSE_ONLY = "instantiated by launch<A_CONV3> through an AMODE-generic statement of a branch that requires !conv at run time (gemm_conv.hip: launch())"
-
 LEDGER = {
     # dense
-    _g(128, 128, 0, 2, 2, False, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=0"),
-    _g(128, 128, 0, 2, 2, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=0"),
-    _g(128, 128, 0, 2, 2, True, 2, 2, False, 0, 0, 0): ("knob", "AE_GEMM_WK=2"),
-    _g(128, 128, 0, 2, 4, False, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=1"),
-    _g(128, 128, 0, 2, 4, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=1"),
     _g(128, 128, 0, 4, 2, False, 1, 2, False, 0, 0, 0): ("default", ["g128_rs"]),
     _g(128, 128, 0, 4, 2, True, 1, 2, False, 0, 0, 0): ("default", ["g128_short"]),
     _g(128, 128, 0, 4, 2, True, 1, 2, False, 0, 1, 0): ("default", ["g128_wa", "g128_wa_a2", "g128_wa_f32"]),
     _g(128, 128, 0, 4, 2, True, 1, 2, False, 0, 1, 1): ("default", ["g128_wa_rs"]),
     _g(128, 128, 0, 4, 2, True, 1, 2, False, 0, 1, 2): ("default", ["g128_wa_ln"]),
-    _g(128, 128, 0, 4, 2, True, 1, 2, True, 0, 0, 0): ("knob", "AE_GEMM_WA=1"),
     _g(128, 128, 0, 4, 2, True, 1, 2, True, 0, 1, 0): ("default", ["g128_wa_cs"]),
     _g(128, 128, 0, 4, 2, True, 1, 3, False, 0, 0, 0): ("default", ["g128_ring"]),
     _g(128, 128, 0, 4, 2, True, 1, 3, False, 0, 0, 1): ("default", ["g128_ring_rs"]),
     _g(128, 128, 0, 4, 2, True, 1, 3, False, 0, 0, 2): ("default", ["g128_ring_ln"]),
-    _g(128, 160, 0, 2, 2, False, 1, 2, False, 0, 0, 0): ("unreachable", "launch() demotes a 128x160 pick to 128x64 for A_DENSE (gemm_conv.hip: `if (pick == 3 && (... AMODE == A_DENSE ...)) pick = 1`)"),
-    _g(128, 160, 0, 2, 2, True, 1, 2, False, 0, 0, 0): ("unreachable", "launch() demotes a 128x160 pick to 128x64 for A_DENSE (gemm_conv.hip: `if (pick == 3 && (... AMODE == A_DENSE ...)) pick = 1`)"),
-    _g(128, 64, 0, 2, 2, False, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=0"),
-    _g(128, 64, 0, 2, 2, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=0"),
     _g(128, 64, 0, 4, 2, False, 1, 2, False, 0, 0, 0): ("default", ["g128x64_rs"]),
     _g(128, 64, 0, 4, 2, True, 1, 2, False, 0, 0, 0): ("default", ["g128x64"]),
     _g(192, 128, 0, 4, 2, True, 1, 3, False, 0, 0, 0): ("default", ["g192x128_ring"]),
-    _g(192, 320, 0, 2, 4, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_PP=59"),
     _g(192, 320, 0, 2, 4, True, 1, 2, False, 0, 3, 0): ("default", ["g320_pp", "g320_pp_a2"]),
-    _g(192, 320, 0, 4, 2, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_PP=55"),
     _g(192, 320, 0, 4, 2, True, 1, 2, False, 0, 3, 0): ("default", ["g320_geglu"]),
     _g(192, 320, 0, 4, 2, True, 1, 2, False, 0, 3, 2): ("default", ["g320_ln_geglu", "g320_ln_xetail"]),
     _g(64, 64, 0, 2, 2, False, 1, 2, False, 0, 0, 0): ("default", ["g64_rs"]),
     _g(64, 64, 0, 2, 2, True, 1, 2, False, 0, 0, 0): ("default", ["g64"]),
     _g(64, 64, 0, 2, 2, True, 1, 3, False, 0, 0, 0): ("default", ["g64_ring", "g64_ring_a2"]),
     # conv
-    _g(128, 128, 1, 2, 2, False, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=0"),
-    _g(128, 128, 1, 2, 2, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=0"),
-    _g(128, 128, 1, 2, 2, True, 2, 2, False, 0, 0, 0): ("knob", "AE_GEMM_WK=2"),
-    _g(128, 128, 1, 2, 4, False, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=1"),
-    _g(128, 128, 1, 2, 4, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_W8=1"),
     _g(128, 128, 1, 4, 2, False, 1, 2, False, 0, 0, 0): ("default", ["c128_rs", "c128_splitk_rs"]),
-    _g(128, 128, 1, 4, 2, True, 1, 2, False, 0, 0, 0): ("knob", "AE_GEMM_WA=2"),
     _g(128, 128, 1, 4, 2, True, 1, 2, False, 0, 1, 0): ("default", ["c128_wa", "c128_splitk", "cs_48x64_b3_l2_640", "cs_48x64_b6_l3_1280", "c128_ups_zero", "up2_128"]),
-    _g(128, 128, 1, 4, 2, True, 1, 2, True, 0, 0, 0): ("knob", "AE_GEMM_WA=2"),
     _g(128, 128, 1, 4, 2, True, 1, 2, True, 0, 1, 0): ("default", ["c128_wa_cs", "up2_128_cs"]),
-    _g(128, 128, 1, 4, 2, True, 1, 3, False, 0, 0, 0): ("knob", "AE_CONV_DEEP=1"),
     _g(128, 160, 1, 2, 2, False, 1, 2, False, 0, 0, 0): ("default", ["c160_rs"]),
     _g(128, 160, 1, 2, 2, True, 1, 2, False, 0, 0, 0): ("default", ["c160"]),
     _g(128, 64, 1, 2, 2, False, 1, 2, False, 0, 0, 0): ("default", ["c64x128_rs"]),
     _g(128, 64, 1, 2, 2, True, 1, 2, False, 0, 0, 0): ("default", ["c64x128_tile"]),
-    _g(128, 64, 1, 4, 2, False, 1, 2, False, 0, 0, 0): ("unreachable", "the 8-wave 128x64 tile is dense-only (gemm_conv.hip: `pick == 1 && w8 && !conv`); the AE_LAUNCH macro instantiates it for A_CONV3"),
-    _g(128, 64, 1, 4, 2, True, 1, 2, False, 0, 0, 0): ("unreachable", "the 8-wave 128x64 tile is dense-only (gemm_conv.hip: `pick == 1 && w8 && !conv`); the AE_LAUNCH macro instantiates it for A_CONV3"),
-    _g(192, 128, 1, 4, 2, True, 1, 3, False, 0, 0, 0): ("unreachable", _DENSE_ONLY + ": the 192x128 ring (`!done && deep_pref && !conv && ...`)"),
     _g(192, 320, 1, 2, 4, True, 1, 2, False, 0, 0, 0): ("default", ["c320_ups", "c320_ups_zero", "cs_f5_ups"]),
     _g(192, 320, 1, 2, 4, True, 1, 2, False, 0, 3, 0): ("default", ["c320_tap_w40", "c320_tap_k0", "c320_s2", "cs_64x96_b3_l2_320", "cs_64x80_b3_l2_640",
                                                                       "cs_64x80_b6_l3_1280", "cs_64x80_b6_l3_1280_k0", "cs_64x96_b6_l3_1280",
@@ -243,10 +217,8 @@ LEDGER = {
     _g(192, 320, 1, 2, 4, True, 1, 2, True, 0, 0, 0): ("default", ["c320_ups_cs"]),
     _g(192, 320, 1, 2, 4, True, 1, 2, True, 0, 3, 0): ("default", ["c320_tap_w56_cs", "c320_tap_k0_cs", "up2_192_cs"]),
     _g(192, 320, 1, 2, 4, True, 1, 2, True, 0, 4, 0): ("default", ["c320_slab_cs_b11", "c320_slab_m32_w16", "c320_wrap_w16h11"]),
-    _g(192, 320, 1, 4, 2, True, 1, 2, False, 0, 0, 0): ("unreachable", "the 4x2-wave 192x320 plain loop serves GEGLU only (gemm_conv.hip: `else if (a.epi == EPI_GEGLU)`); a conv's epilogue is never GEGLU"),
     _g(64, 64, 1, 2, 2, False, 1, 2, False, 0, 0, 0): ("default", ["c64_rs"]),
     _g(64, 64, 1, 2, 2, True, 1, 2, False, 0, 0, 0): ("default", ["c64", "c64_s2", "c64_ups_zero"]),
-    _g(64, 64, 1, 2, 2, True, 1, 3, False, 0, 0, 0): ("unreachable", _DENSE_ONLY + ": the 64x64 ring (`deep_pref && glds && !conv && ...`)"),
     "splitk_reduce_kernel": ("default", ["c128_splitk", "cs_64x96_b3_l2_640", "cs_64x80_b6_l3_1280", "cs_64x96_b6_l3_2560", "cs_64x80_b6_l3_1920",
                                          "cs_64x80_b6_l3_640", "cs_48x64_b6_l3_1280", "cs_f7", "cs_f8", "cs_f3", "cs_f4_slab", "cs_f4_tap",
                                          "cs_f5_ups", "cs_s2_f2", "cs_s2_f5"]),
@@ -256,11 +228,6 @@ LEDGER = {
     _af(160, 1, True, 0, 0, 1, False, False, 4, 3): ("default", ["a160_seg2_long", "a160_seg2_long_300"]),
     _af(160, 1, True, 0, 0, 1, False, True, 4, 3): ("default", ["a160_skv_seg2", "a160_skv_seg2_300"]),
     _af(160, 2, False, 0, 0, 1, False, False, 4, 3): ("default", ["a160_320", "a160_384"]),
-    _af(160, 2, False, 0, 1, 1, False, False, 4, 3): ("unreachable", "ae_attn_fast_launch refuses D = 160 with a rel-pos bias (attention_fast.hip: `return (a.rel_h || !f160) ? AE_ERR_UNSUPPORTED`)"),
-    _af(160, 2, False, 0, 2, 1, False, False, 4, 3): ("unreachable", "ae_attn_fast_launch refuses D = 160 with a rel-pos bias (attention_fast.hip: `return (a.rel_h || !f160) ? AE_ERR_UNSUPPORTED`)"),
-    _af(160, 3, False, 0, 0, 1, False, False, 4, 3): ("unreachable", "launch_fast<160> returns at `if constexpr (D > 96)` before the OCC-3 statements that instantiate it"),
-    _af(160, 3, False, 0, 0, 1, True, False, 4, 3): ("unreachable", "launch_fast<160> returns at `if constexpr (D > 96)` before the OCC-3 statements that instantiate it"),
-    _af(40, 3, False, 0, 0, 1, False, False, 4, 3): ("knob", "AE_ATTN_V=0"),
     _af(40, 3, False, 0, 0, 1, False, True, 4, 3): ("default", ["a40_skv", "a40_skv_ng1", "a40_skv_ng4", "a40_skv_ng8"]),
     _af(40, 3, False, 0, 0, 1, True, False, 4, 3): ("default", ["a40_vsplit", "a40_4032_b3"]),
     _af(40, 3, False, 0, 0, 2, True, False, 4, 3): ("default", ["a40_qg2"]),
@@ -272,10 +239,8 @@ LEDGER = {
     _af(80, 2, False, 0, 3, 1, False, True, 7, 4): ("default", ["a80_relwin"]),
     _af(80, 2, True, 0, 0, 1, False, False, 4, 3): ("default", ["a80_seg2_long"]),
     _af(80, 2, True, 0, 0, 1, False, True, 4, 3): ("default", ["a80_skv_seg2", "a80_skv_seg2_1000"]),
-    _af(80, 3, False, 0, 0, 1, False, False, 4, 3): ("knob", "AE_ATTN_V=0"),
     _af(80, 3, False, 0, 0, 1, True, False, 4, 3): ("default", ["a80_vsplit", "a80_vsplit_1280", "a80_vsplit_1500"]),
     "attn_pipe_kernel<40, 128, false>": ("default", ["a40_pipe128", "a40_pipe128_nq4000", "a40_pipe_6144", "a40_pipe_5120"]),
-    "attn_pipe_kernel<40, 128, true>": ("knob", "AE_ATTN_PV16=1"),
     "attn_pipe_kernel<40, 64, false>": ("default", ["a40_pipe64", "a40_pipe64_b6"]),
 }
 

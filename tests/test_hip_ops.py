@@ -196,62 +196,6 @@ def test_layernorm_folded_into_gemm(ops, M, C, N, epi):
         ops._gemm_ln(x[:64], wq, c, None, E, None, None, st[:64].contiguous(), s, 1e-5)
 
 
-def test_cross_attention_half_fused_inside_the_product():
-    """The opt-in plan (AE_XATTN_FUSED=1) end to end: a 4-step, 3-branch-CFG edit of the bench model at 64x64 with the fused cross-attention launches (K/V images from
-    prepare_conditioning) against the same edit on the default plan, with the distance of a second proven plan (feed-forward as two launches) measured in the same run as the yardstick;
-    the switches are read once per process, so tools/xattn_module_check.py runs one child per setting.  The rest of the suite runs the product default (the switch off)."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "xattn_module_check.py")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-    print(r.stdout[-1500:])
-    assert r.returncode == 0, r.stdout[-3000:]
-    assert "[base] " in r.stdout and "AE_XATTN_FUSED=0: fused cross-attention launches in the profiled edit: 0" in r.stdout
-    assert "AE_XATTN_FUSED=1: fused cross-attention launches in the profiled edit: 0" not in r.stdout and "AE_XATTN_FUSED=1" in r.stdout and " OK" in r.stdout
-
-
-@pytest.mark.parametrize("B,HW_side,Cin,Cout", [(12, 16, 1280, 1280), (12, 8, 1280, 1280), (12, 16, 2560, 1280), (12, 8, 2560, 1280), (12, 16, 640, 1280), (4, 16, 1280, 1280)])
-def test_groupnorm_folds_the_splitk_partials_bit_identical(ops, B, HW_side, Cin, Cout):
-    """openaimodel.py:262-272 at the 16x16 / 8x8 levels (round 6): conv1's split-K plan stopped at its fp32 partials (ae_conv3x3_partials_bf16) and the GroupNorm + SiLU
-    folding the K ranges, the bias and the time-embedding vector itself (ae_groupnorm_splitk_nhwc_bf16) against conv3x3 (with its reduce launch) followed by groupnorm:
-    the same adds in the same order and one rounding -> bit-identical, with and without bias / vector, strided vector rows; refusals outside the envelope."""
-    H = W = HW_side
-    ops._GN_SPLITK, knob = True, ops._GN_SPLITK          # opt-in in the product (measured slower in the graph: ops.py); the operators are tested regardless
-    try:
-        _splitk_fold_case(ops, B, H, W, Cin, Cout)
-    finally:
-        ops._GN_SPLITK = knob
-
-
-def _splitk_fold_case(ops, B, H, W, Cin, Cout):
-    if not ops.conv3x3_gn_splitk_ok(B, H, W, Cin, Cout):
-        pytest.skip(f"the plan does not cut K for B={B} {H}x{W} {Cin}->{Cout}")
-    g = torch.Generator().manual_seed(B + H + Cin)
-    x = torch.randn(B * H * W, Cin, generator=g).bfloat16().to(DEV)
-    w = ops.pack_conv3x3((torch.randn(Cout, Cin, 3, 3, generator=g) / (3.0 * Cin ** 0.5)).to(DEV))
-    bias = torch.randn(Cout, generator=g).to(DEV)
-    emb_all = torch.randn(B, 3 * Cout, generator=g).to(DEV)
-    addvec = emb_all[:, Cout:2 * Cout]                               # strided rows, as the batched time-embedding projection hands them over
-    gamma, beta = (1.0 + 0.1 * torch.randn(Cout, generator=g)).to(DEV), (0.1 * torch.randn(Cout, generator=g)).to(DEV)
-    for bz, av in ((bias, addvec), (None, addvec), (bias, None), (None, None)):
-        for silu in (True, False):
-            h, _, _ = ops.conv3x3(x, w, bz, B, H, W, addvec=av)
-            ref = ops.groupnorm(h, gamma, beta, B, H * W, 1e-5, silu=silu)
-            part, sk = ops.conv3x3_partials(x, w, B, H, W)
-            assert part.shape == (sk, B * H * W, Cout) and 2 <= sk <= 8
-            got = ops.groupnorm_splitk(part, bz, av, gamma, beta, B, H * W, 1e-5, silu=silu)
-            assert torch.equal(got, ref), (bz is not None, av is not None, silu, float((got.float() - ref.float()).abs().max()))
-    assert torch.equal(ops.groupnorm_splitk(part, None, None, gamma, beta, B, H * W, 1e-5), got), "run-to-run bit-equal"
-    with pytest.raises(ValueError):
-        ops.groupnorm_splitk(part[:, :, :Cout - 8], None, None, gamma, beta, B, H * W, 1e-5)          # not contiguous
-    with pytest.raises(ValueError):
-        ops.groupnorm_splitk(part, None, emb_all, gamma, beta, B, H * W, 1e-5)                          # vector of the wrong width
-    assert ops.lib.ae_groupnorm_splitk_supported(B, 1024, Cout, 32, sk) == 0 and ops.lib.ae_groupnorm_splitk_supported(B, H * W, Cout, 32, 1) == 0
-    assert not ops.conv3x3_gn_splitk_ok(12, 64, 64, 320, 320) and not ops.conv3x3_gn_splitk_ok(1, 8, 8, 64, 64)   # maps beyond 256 positions; a K loop too short to cut
-    with pytest.raises(ValueError):
-        ops.conv3x3_partials(x[:64, :64].contiguous(), ops.pack_conv3x3(torch.zeros(64, 64, 3, 3, device=DEV)), 1, 8, 8)   # nine K tiles: the plan does not cut K
-
-
 @pytest.mark.parametrize("M,H,res", [(192, 1280, True), (500, 1280, True), (777, 64, False), (1000, 256, True), (49152, 1280, True), (49000, 1280, True)])
 def test_feed_forward_fused_one_launch(ops, M, H, res):
     """attention.py:49-76 behind norm3 (:271-275) as ONE launch (ae_ff_fused_bf16, round 6): LayerNorm -> GEGLU projection -> exact-erf gate -> ff2
@@ -308,61 +252,6 @@ def test_feed_forward_fused_one_launch(ops, M, H, res):
     z4 = ops.ff_fused(xd, gamma.to(DEV), beta.to(DEV), 1e-5, w1p, b1p, w2img, b2.to(DEV), residual=xd if res else None, w3=w3.to(DEV, BF), b3=b3.to(DEV),
                       residual3=r3.to(DEV, BF))
     assert torch.equal(z3, z4), "the fused feed-forward + proj_out is not run-to-run bit-equal"
-
-
-@pytest.mark.parametrize("B,N,Nk,T", [(1, 128, 78, 4), (2, 256, 77, 0), (3, 384, 80, 16), (12, 4096, 78, 4)])
-def test_cross_attention_half_fused_one_launch(ops, B, N, Nk, T):
-    """attention.py:273 `x = attn2(norm2(x), context) + x` as ONE launch (ae_xattn_fused_bf16, round 6): LayerNorm -> to_q -> softmax(QK^T)V over the text keys (+ the gated expert
-    segment of DESIGN.md §6) -> to_out + bias + residual, with q / logits / probabilities / attention output kept in registers.
-      1. against the fp64 module arithmetic on the same bf16 inputs (operator tolerance);
-      2. no worse than the three-launch HIP path it replaces (LayerNorm + q projection, short-K/V attention with the second segment, to_out + residual) by more than 25 % + 5e-4;
-      3. run-to-run bit-equal; key counts 77 / 78 / 80 (padding masks), no expert segment, a full 16-key expert segment; samples never mix (per-sample K | V and gate)."""
-    C, H, D = 320, 8, 40
-    M = B * N
-    # the kernel is opt-in in the MODULE (AE_XATTN_FUSED, default off: measured slower); this operator test calls it directly, the rest of the suite runs the product default
-    assert ops.lib.ae_xattn_fused_covers(M, C, H, D, N, Nk, T) == 1 and ops.lib.ae_xattn_fused_supported(M, C, H, D, N, Nk, T) == int(os.environ.get("AE_XATTN_FUSED", "0") != "0")
-    g = torch.Generator().manual_seed(B * 1000 + Nk + T)
-    x = q(torch.randn(M, C, generator=g) * 1.3 + torch.randn(M, 1, generator=g) * 2.0)
-    wq = torch.randn(C, C, generator=g) / C ** 0.5
-    wo = torch.randn(C, C, generator=g) / C ** 0.5
-    bo = 0.1 * torch.randn(C, generator=g)
-    gamma, beta = 1.0 + 0.2 * torch.randn(C, generator=g), 0.2 * torch.randn(C, generator=g)
-    kv = q(torch.randn(B * Nk, 2 * C, generator=g))
-    kv_ip = q(torch.randn(B * T, 2 * C, generator=g)) if T else None
-    gate = torch.rand(B, generator=g) if T else None
-    scale = D ** -0.5
-    # fp64 reference
-    xn = F.layer_norm(x.double(), (C,), gamma.double(), beta.double(), 1e-5)
-    qq = (xn @ q(wq).double().t()).reshape(B, N, H, D).permute(0, 2, 1, 3)
-    kk = kv.double().reshape(B, Nk, 2, H, D)
-    att = torch.softmax(qq @ kk[:, :, 0].permute(0, 2, 3, 1) * scale, -1) @ kk[:, :, 1].permute(0, 2, 1, 3)
-    if T:
-        ki = kv_ip.double().reshape(B, T, 2, H, D)
-        att = att + gate.double()[:, None, None, None] * (torch.softmax(qq @ ki[:, :, 0].permute(0, 2, 3, 1) * scale, -1) @ ki[:, :, 1].permute(0, 2, 1, 3))
-    ref = (att.permute(0, 2, 1, 3).reshape(M, C) @ q(wo).double().t() + bo.double() + x.double()).float()
-    xd, gd, bd = x.to(DEV, BF), gamma.to(DEV), beta.to(DEV)
-    wq_img, wo_img = ops.pack_xattn_wq(wq.to(DEV)), ops.pack_xattn_wo(wo.to(DEV))
-    kv_img = ops.pack_xattn_kv(kv.to(DEV, BF), None if kv_ip is None else kv_ip.to(DEV, BF), B, Nk, T)
-    assert kv_img.shape == (B, 8, ops.lib.ae_xattn_fused_kv_bytes() // 2)
-    gated = None if gate is None else gate.to(DEV)
-    y = ops.xattn_fused(xd, gd, bd, 1e-5, wq_img, kv_img, gated, wo_img, bo.to(DEV), N, Nk, T, scale)
-    # the three launches it replaces
-    qd = ops.ln_gemm(xd, gd, bd, 1e-5, wq.to(DEV, BF))
-    kvd = kv.to(DEV, BF)
-    qs, ks = (N * C, D, C), (Nk * 2 * C, D, 2 * C)
-    if T:
-        kid = kv_ip.to(DEV, BF)
-        ksi = (T * 2 * C, D, 2 * C)
-        o = ops.attention(qd, kvd, kvd[:, C:], B, H, N, Nk, D, scale, qs, ks, ks, seg2=(kid, kid[:, C:], T, ksi, ksi, gated))
-    else:
-        o = ops.attention(qd, kvd, kvd[:, C:], B, H, N, Nk, D, scale, qs, ks, ks)
-    y3 = ops.gemm(o.reshape(M, C), wo.to(DEV, BF), bias=bo.to(DEV), residual=xd)
-    e1, e3 = rel_l2(y.float().cpu(), ref), rel_l2(y3.float().cpu(), ref)
-    print(f"fused cross-attention half B={B} N={N} Nk={Nk}+{T}: rel-L2 fused {e1:.3e}, three launches {e3:.3e}")
-    check_close(y, ref, rl2=5e-3, mabs=3e-2, what=f"fused cross-attention half B={B} N={N} Nk={Nk}+{T}")
-    assert e1 <= 1.25 * e3 + 5e-4, (e1, e3)
-    y2 = ops.xattn_fused(xd, gd, bd, 1e-5, wq_img, kv_img, gated, wo_img, bo.to(DEV), N, Nk, T, scale)
-    assert torch.equal(y, y2), "the fused cross-attention half is not run-to-run bit-equal"
 
 
 @pytest.mark.parametrize("B,H,W,Cout", [(2, 16, 16, 64), (1, 5, 7, 320), (12, 64, 64, 320)])
@@ -865,14 +754,11 @@ def test_attention_pipelined_equals_two_group_kernel():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "attn_pipe_check.py"), "3", "7k0", "7", "7p"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1200)
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "attn_pipe_check.py"), "3", "7k0", "7"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1200)
     print(r.stdout[-2000:])
     assert r.returncode == 0, r.stdout[-3000:]
-    # four variants: the two-group kernel, the pipelined kernel on 64-key tiles (round 5) and on 128-key tiles (round 6, the default), and — opt-in, AE_ATTN_PV16=1,
-    # measured slower in the graph — the 128-key form with the PV products on 48 rows of v_mfma_f32_16x16x32_bf16: another summation order inside PV,
-    # so it is held to 2.5e-3 of the two-group kernel's outputs (3.9e-5 at the time of writing) instead of to identity
+    # three variants: the two-group kernel, the pipelined kernel on 64-key tiles (round 5) and on 128-key tiles (round 6, the default)
     assert r.stdout.count("bit-identical on all") == 2 and "FAIL" not in r.stdout and "bit-identical: False" not in r.stdout
-    assert r.stdout.count("tolerance, not identity") == 1
 
 
 def test_conv3x3_linearity_and_groupnorm_scale_invariance_full_size(ops):

@@ -140,7 +140,7 @@ def test_no_vgpr_write_to_the_sources_of_a_running_mfma(tmp_path):
     import isa_audit as A
     asm = A.compile_asm(["attention_fast.hip"], str(tmp_path))[0]
     res = A.mfma_source_overwrites(asm, "attn_fast_kernel<")
-    assert len(res) >= 20
+    assert len(res) == 16, sorted(res)              # every attn_fast_kernel row of the route ledger (tests/route_cases.py)
     kinds = {"qg2": r"attn_fast_kernel<\d+, \d+, (true|false), 0, 0, 2,", "short_kv": r"attn_fast_kernel<\d+, \d+, (true|false), 0, 0, 1, false, true",
              "short_kv_seg2_d160": r"attn_fast_kernel<160, 1, true, 0, 0, 1, false, true", "sam_window": r"attn_fast_kernel<80, 2, false, 0, 3, 1, false, true, 7, 4>",
              "sam_global": r"attn_fast_kernel<80, 2, false, 0, 2,"}
@@ -151,17 +151,16 @@ def test_no_vgpr_write_to_the_sources_of_a_running_mfma(tmp_path):
     # round 5: the software-pipelined kernel — its 14 MFMAs per step are chained into one program order and every fragment is tied to the MFMA two
     # positions behind its last reader (the first listing of that kernel, without the ties, had 186 such writes)
     pipe = A.mfma_source_overwrites(asm, "attn_pipe_kernel<")
-    assert len(pipe) == 3                           # keys per tile 64 (round 5), 128 (round 6), and 128 with the 48-row 16x16x32 PV products (round 6, opt-in)
+    assert len(pipe) == 2                           # keys per tile 64 (round 5) and 128 (round 6)
     for k, hits in pipe.items():
         assert not hits, (k, hits[:3])
     rows = [(n, md, loop) for n, md, loop in A.audit_named(asm) if "attn_pipe_kernel<" in n]
-    assert len(rows) == 3
+    assert len(rows) == 2
     for n, md, loop in rows:
         steps = 4 if "<40, 128" in n else 2         # 32-key blocks (pipeline steps) per loop trip = per tile
-        pv16 = "true>" in n                         # 6 logit MFMAs + 12 PV MFMAs of 16x16x32 per step instead of 6 + 8 of 32x32x16; 8 lane swaps more
         assert md["vgpr_spill_count"] == "0" and md["private_segment_fixed_size"] == "0" and int(md["vgpr_count"]) <= 256, (n, md)   # two waves per SIMD
-        assert loop[0] == (18 if pv16 else 14) * steps and loop[2] == 0, (n, loop)   # one tile per loop trip, no scratch traffic
-        assert loop[7] <= (88 if pv16 else 80) * steps, (n, loop)     # VALU per trip (74 per step at the time of writing: 32 exp2, 16 converts, 17 max3, addresses): register copies would show here
+        assert loop[0] == 14 * steps and loop[2] == 0, (n, loop)   # one tile per loop trip, no scratch traffic
+        assert loop[7] <= 80 * steps, (n, loop)     # VALU per trip (74 per step at the time of writing: 32 exp2, 16 converts, 17 max3, addresses): register copies would show here
 
 
 def test_fused_feed_forward_stream_is_the_hand_placed_one(tmp_path):
@@ -195,23 +194,6 @@ def test_fused_feed_forward_stream_is_the_hand_placed_one(tmp_path):
         assert sum("v_accvgpr" in x for x in seg) <= 2, [x for x in seg if "v_accvgpr" in x][:5]
     res = A.mfma_source_overwrites(asm, "ff_fused_kernel<")
     assert len(res) == 2
-    for k, hits in res.items():
-        assert not hits, (k, hits[:3])
-
-
-def test_fused_cross_attention_stream_keeps_its_mfma_sources(tmp_path):
-    """Round 6 (csrc/xattn_fused.hip, opt-in): the same hand-placed technique as the fused feed-forward — asm MFMAs hipcc neither pads nor tracks, with q, probabilities and
-    attention outputs written by VALU and consumed as MFMA operands a few instructions later.  The listing must show no spills / scratch and no VALU result landing in a source
-    register of an MFMA before two further MFMAs were issued or a read of that MFMA's (or a later one's) result (the first listing had 26 such writes: pack temporaries in the W
-    fragments of a phase's last slots, the row maximum in the q operands)."""
-    import isa_audit as A
-    asm = A.compile_asm(["xattn_fused.hip"], str(tmp_path))[0]
-    rows = [(n, md, loop) for n, md, loop in A.audit_named(asm) if "xattn_fused_kernel" in n]
-    assert len(rows) == 1
-    _, md, _ = rows[0]
-    assert md["vgpr_spill_count"] == "0" and md["private_segment_fixed_size"] == "0" and int(md["agpr_count"]) >= 160, md
-    res = A.mfma_source_overwrites(asm, "xattn_fused_kernel")
-    assert len(res) == 1
     for k, hits in res.items():
         assert not hits, (k, hits[:3])
 

@@ -58,13 +58,8 @@ def test_ledger_rows_are_well_formed():
     assert len(ids) == len(RC.CASES), "duplicate case ids"
     for key, row in RC.LEDGER.items():
         kind, what = row
-        assert kind in ("default", "knob", "unreachable"), (key, kind)
-        if kind == "default":
-            assert what and all(c in ids for c in what), (key, [c for c in what if c not in ids])
-        elif kind == "knob":
-            assert re.fullmatch(r"AE_[A-Z0-9_]+=\S+", what), (key, what)
-        else:
-            assert len(what) > 20, (key, "an unreachable row says why")
+        assert kind == "default", (key, kind)
+        assert what and all(c in ids for c in what), (key, [c for c in what if c not in ids])
     for c in RC.CASES:
         assert c["op"] in ("conv", "up2", "gemm", "ln", "attn"), c
     # every case asserts a route: it appears in at least one `default` row
@@ -79,7 +74,9 @@ def test_ledger_rows_are_well_formed():
 def test_ledger_equals_the_compiled_instantiations(tmp_path):
     keys = compiled_instantiations(tmp_path)
     assert len(keys) == len(set(keys)), "a kernel key appears twice"
-    assert sum(k.startswith("gemm_kernel<") for k in keys) > 40 and sum(k.startswith("attn_") for k in keys) > 20, keys
+    # (equality with the ledger's own count per family: a regular expression that silently finds nothing cannot pass)
+    for family in ("gemm_kernel<", "attn_"):
+        assert sum(k.startswith(family) for k in keys) == sum(k.startswith(family) for k in RC.LEDGER) > 0, (family, keys)
     compiled, ledger = set(keys), set(RC.LEDGER)
     assert not compiled - ledger, f"instantiations without a ledger row (classify them in tests/route_cases.py): {sorted(compiled - ledger)}"
     assert not ledger - compiled, f"ledger rows for instantiations the default build no longer compiles: {sorted(ledger - compiled)}"

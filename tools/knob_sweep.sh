@@ -8,9 +8,7 @@ run() { ( env "$@" timeout 300 python bench.py --steps 3 --warmup 1 --full --no-
 run AE_DEFAULT=1
 run AE_CONV_T320_SPLITK=1
 run AE_CONV_T320_SPLITK=3
-run AE_GEMM_WK=1
 run AE_GEMM_DEEP=0
-run AE_CONV_DEEP=0
 run AE_DEFAULT=1
 run AE_GEMM_T320=15
 run AE_GEMM_T320=3
@@ -20,7 +18,5 @@ run AE_LN_ROWS=0
 run AE_DEFAULT=1
 run AE_GN_COLSTATS=0
 run AE_GEMM_DEEP64_MAX=256
-run AE_ATTN_V=1
-run AE_GEMM_W8=1
 run AE_DEFAULT=1
 } 2>&1 | tee $OUT/knob_sweep.txt

@@ -1,5 +1,5 @@
 // Ping-pong lab (round 4): standalone harness around anyedit_amd/csrc/gemm_conv.hip (no Python / torch: a gpurun visit costs seconds).
-// Times the 192x320-tile launches of the UNet at batch 12 under AE_GEMM_PP (read from the environment by the launcher) and, in
+// Times the 192x320-tile launches of the UNet at batch 12 and, in
 // -DAE_GEMM_LAB builds, prints where one SIMD's two waves (wave 0 = group 0, wave 4 = group 1) of a mid-grid block spend their cycles per K tile.
 // Variants are compile-time macros of gemm_conv.hip: -DAE_PP_LAB=1|2|3 (ablations: results are wrong by construction), -DAE_PP_DMA_FIRST=1,
 // -DAE_PP_PRIO=0, ...   Parity is covered by tests/ (the product build).
@@ -106,8 +106,7 @@ static void dense(int M, int N, int K, int epi, const char* tag) {
 }
 
 int main(int argc, char** argv) {
-    const char* pp = getenv("AE_GEMM_PP");
-    printf("# AE_GEMM_PP=%s  AE_PP_LAB=%d AE_PP_PRIO=%d AE_PP_DMA_FIRST=%d\n", pp ? pp : "(default)", AE_PP_LAB, AE_PP_PRIO, AE_PP_DMA_FIRST);
+    printf("# AE_PP_LAB=%d AE_PP_PRIO=%d AE_PP_DMA_FIRST=%d\n", AE_PP_LAB, AE_PP_PRIO, AE_PP_DMA_FIRST);
     const bool all = argc > 1 && argv[1][0] == 'x';
     if (argc > 1 && argv[1][0] == 'c') {   // one case only (PMC passes)
         conv(12, 64, 960, 320, 1, "conv L1 960->320 @64 kmajor");
