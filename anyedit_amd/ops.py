@@ -1460,7 +1460,14 @@ def layernorm_window_ok(C):
     return bool(lib.ae_layernorm_window_supported(int(C)))
 
 
-def layernorm_window_partition(x, gamma, beta, eps, B, H, W, ws):
+def _out_rows(out, rows, C, name):
+    """`out`: None, or the caller's contiguous bf16 [rows, C] buffer the kernel writes to"""
+    if out is not None and (out.dtype != BF16 or tuple(out.shape) != (rows, C) or not out.is_contiguous()):
+        raise ValueError(f"{name}: out must be a contiguous bf16 [{rows}, {C}] tensor, got {tuple(out.shape)}")
+    return out
+
+
+def layernorm_window_partition(x, gamma, beta, eps, B, H, W, ws, out=None):
     """window_partition(LayerNorm(x)) in one launch (SAM Block norm1 + partition, image_encoder.py:166-173): x [B*H*W, C] image rows ->
     ([B*nH*nW*ws*ws, C] window rows with zero padding rows, (Hp, Wp))."""
     _chk(x, BF16, "layernorm_window_partition.x", 2)
@@ -1470,13 +1477,15 @@ def layernorm_window_partition(x, gamma, beta, eps, B, H, W, ws):
     if not x.is_contiguous() or x.shape[0] != B * H * W or gamma.numel() != C or beta.numel() != C:
         raise ValueError("layernorm_window_partition: x must be contiguous [B*H*W, C] rows, gamma / beta [C]")
     nH, nW = (H + ws - 1) // ws, (W + ws - 1) // ws
-    out = torch.empty(B * nH * nW * ws * ws, C, dtype=BF16, device=x.device)
+    out = _out_rows(out, B * nH * nW * ws * ws, C, "layernorm_window_partition")
+    if out is None:
+        out = torch.empty(B * nH * nW * ws * ws, C, dtype=BF16, device=x.device)
     check(lib.ae_layernorm_window_bf16(_p(x), None, _p(gamma), _p(beta), _p(out), None, B, H, W, C, ws, 1, eps, _s()),
           "ae_layernorm_window_bf16")
     return out, (nH * ws, nW * ws)
 
 
-def window_merge_layernorm(windows, shortcut, gamma, beta, eps, B, H, W, ws):
+def window_merge_layernorm(windows, shortcut, gamma, beta, eps, B, H, W, ws, out=None, xsum_out=None):
     """(x, LayerNorm(x)) with x = shortcut + window_unpartition(windows) in one launch (SAM Block :175-181: un-partition, residual add, norm2)."""
     _chk(windows, BF16, "window_merge_layernorm.windows", 2)
     _chk(shortcut, BF16, "window_merge_layernorm.shortcut", 2)
@@ -1487,7 +1496,9 @@ def window_merge_layernorm(windows, shortcut, gamma, beta, eps, B, H, W, ws):
     if not (windows.is_contiguous() and shortcut.is_contiguous()) or shortcut.shape[0] != B * H * W or tuple(windows.shape) != (nwin_rows, C) \
             or gamma.numel() != C or beta.numel() != C:
         raise ValueError("window_merge_layernorm: windows must be contiguous [B*nH*nW*ws*ws, C], shortcut [B*H*W, C], gamma / beta [C]")
-    xsum, y = torch.empty_like(shortcut), torch.empty_like(shortcut)
+    xsum, y = _out_rows(xsum_out, B * H * W, C, "window_merge_layernorm"), _out_rows(out, B * H * W, C, "window_merge_layernorm")
+    xsum = torch.empty_like(shortcut) if xsum is None else xsum
+    y = torch.empty_like(shortcut) if y is None else y
     check(lib.ae_layernorm_window_bf16(_p(windows), _p(shortcut), _p(gamma), _p(beta), _p(y), _p(xsum), B, H, W, C, ws, 2, eps, _s()),
           "ae_layernorm_window_bf16")
     return xsum, y
@@ -1792,28 +1803,37 @@ def _grad_target(t, into):
     return into, 1
 
 
-def groupnorm_bwd(x, gamma, beta, dy, B, HW, eps, silu=False, groups=32, x2=None, stat=None, dx_into=None, dx2_into=None):
-    """dx_into / dx2_into: tensors that already hold a gradient of x / x2 — the kernel adds to them in place (no separate add launch) and they are returned."""
+def groupnorm_bwd(x, gamma, beta, dy, B, HW, eps, silu=False, groups=32, x2=None, stat=None, dx_into=None, dx2_into=None, dx_out=None, dx2_out=None):
+    """dx_into / dx2_into: tensors that already hold a gradient of x / x2 — the kernel adds to them in place (no separate add launch) and they are returned.
+    dx_out / dx2_out: the caller's buffers for a gradient that is written, not added (not together with the `_into` of the same tensor)."""
     C1 = x.shape[1]
     C = C1 + (x2.shape[1] if x2 is not None else 0)
-    dx, acc1 = _grad_target(x, dx_into)
-    dx2, acc2 = _grad_target(x2, dx2_into) if x2 is not None else (None, 0)
+    if (dx_into is not None and dx_out is not None) or (dx2_into is not None and dx2_out is not None):
+        raise ValueError("groupnorm_bwd: a gradient is either added to `_into` or written to `_out`")
+    dx, acc1 = _grad_target(x, dx_into) if dx_out is None else (_grad_target(x, dx_out)[0], 0)
+    dx2, acc2 = (_grad_target(x2, dx2_into) if dx2_out is None else (_grad_target(x2, dx2_out)[0], 0)) if x2 is not None else (None, 0)
     ws = torch.empty(lib.ae_groupnorm_bwd_workspace_floats(B, HW, C, groups), dtype=torch.float32, device=x.device)
     check(lib.ae_groupnorm_bwd_nhwc_bf16(_p(x), _p(x2), C1, _p(gamma), _p(beta), _p(_tmp(dy.contiguous())), _p(dx), _p(dx2), B, HW, C, groups,
                                          eps, 1 if silu else 0, _p(ws), _p(_gn_counters(x.device, B)), _p(stat), acc1 | (acc2 << 1), _s()), "ae_groupnorm_bwd_nhwc_bf16")
     return dx, dx2
 
 
-def layernorm_bwd(x, gamma, dy, eps=1e-5, want_param_grads=False, dx_into=None):
+def layernorm_bwd(x, gamma, dy, eps=1e-5, want_param_grads=False, dx_into=None, dx_out=None, dgamma_out=None, dbeta_out=None):
+    """dx_into: added to in place; dx_out / dgamma_out / dbeta_out: the caller's buffers (bf16 like x; fp32 [C]) for results that are written."""
     M, C = x.shape
-    dx, acc = _grad_target(x, dx_into)
+    if dx_into is not None and dx_out is not None:
+        raise ValueError("layernorm_bwd: the gradient is either added to dx_into or written to dx_out")
+    dx, acc = _grad_target(x, dx_into) if dx_out is None else (_grad_target(x, dx_out)[0], 0)
     stat = torch.empty(M, 2, dtype=torch.float32, device=x.device) if want_param_grads else None
     dy = dy.contiguous()
     check(lib.ae_layernorm_bwd_bf16(_p(x), _p(gamma), _p(dy), _p(dx), _p(stat), M, C, eps, acc, _s()), "ae_layernorm_bwd_bf16")
     if not want_param_grads:
         return dx, None, None
-    dg = torch.empty(C, dtype=torch.float32, device=x.device)
-    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    for t in (dgamma_out, dbeta_out):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (C,) or not t.is_contiguous()):
+            raise ValueError("layernorm_bwd: dgamma_out / dbeta_out must be contiguous fp32 [C] tensors")
+    dg = torch.empty(C, dtype=torch.float32, device=x.device) if dgamma_out is None else dgamma_out
+    db = torch.empty(C, dtype=torch.float32, device=x.device) if dbeta_out is None else dbeta_out
     check(lib.ae_layernorm_param_grad_f32(_p(x), _p(dy), _p(stat), _p(dg), _p(db), M, C, _s()), "ae_layernorm_param_grad_f32")
     return dx, dg, db
 

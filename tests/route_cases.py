@@ -1,9 +1,10 @@
-"""Route cases and the route ledger of gemm_conv.hip / attention_fast.hip, shared by tests/test_kernel_routes.py and tools/route_check.py.
+"""Route cases and the route ledger of gemm_conv.hip / attention_fast.hip (CASES, LEDGER: tools/route_check.py) and of norm.hip (NORM_CASES,
+NORM_LEDGER: tools/norm_route_check.py), shared with tests/test_kernel_routes.py.
 
 CASES: one dict per GPU case (op + shape + options); tools/route_check.py builds the seeded operands, runs the op through `ops`, records the
 kernels it launched and checks the output element by element (see that script's docstring for the bound).
 
-LEDGER: one row per kernel instantiation of the two files in the default build, keyed by the template-argument tuple as c++filt prints it
+LEDGER / NORM_LEDGER: one row per kernel instantiation of the three files in the default build, keyed by the template-argument tuple as c++filt prints it
 (`gemm_kernel<192, 320, 1, 2, 4, true, 1, 2, false, 0, 4, 0>`: BM, BN, AMODE (0 dense, 1 conv), WAVES_M, WAVES_N, GLDS, WAVES_K, STAGES,
 CS, LAB, WA, XE; `attn_fast_kernel<D, OCC, SEG2, ABL, BIAS, QG, VSPLIT, SKV, NWV, SKT>`; `attn_pipe_kernel<D, KT, PV16>`).  Each row is
   ("default", [case ids])   reached with no AE_* variable set, by every case listed.
@@ -245,6 +246,154 @@ LEDGER = {
 }
 
 
+# --------------------------------------------------------------------------------------------------- norm.hip: cases
+# (tools/norm_route_check.py runs them; tests/norm_ref.py holds the operands, the float64 reference and the bounds)
+# gn:    ops.groupnorm: B, HW, C, groups; C1 (channels of the first source of a concat input, 0 = one source), silu, cs (statistics from
+#        the producers' per-32-row column sums), stat (ask for (mean, rstd))
+# gnb:   ops.groupnorm_bwd: the same, plus saved (the forward's (mean, rstd) are passed in) and acc (bit 0: dx +=, bit 1: dx2 +=)
+# ln:    ops.layernorm: M, C; align=False offsets gamma / beta by 4 bytes (the rows kernel wants 16-byte aligned parameters)
+# lnb:   ops.layernorm_bwd: M, C, param (parameter gradients), acc
+# lnwin: ops.layernorm_window_partition (mode 1) / ops.window_merge_layernorm (mode 2): B, H, W, C, ws
+# lnact: ops.layernorm_act: M, C, gelu
+def _gn(id, B, HW, C, groups=32, C1=0, silu=False, cs=False, stat=True):
+    return dict(id=id, op="gn", B=B, HW=HW, C=C, groups=groups, C1=C1, silu=silu, cs=cs, stat=stat)
+
+
+def _gnb(id, B, HW, C, groups=32, C1=0, silu=False, saved=True, acc=0):
+    return dict(id=id, op="gnb", B=B, HW=HW, C=C, groups=groups, C1=C1, silu=silu, saved=saved, acc=acc)
+
+
+_LN_ROWS = {320: 8, 640: 16, 1280: 32, 2560: 64}      # C -> L of layernorm_rows_kernel<L, 5> / layernorm_window_kernel<L, 5, mode>
+_NARROW = {8: 1, 16: 2, 24: 4, 64: 8, 104: 16, 256: 32, 512: 64}   # C -> L of layernorm_narrow_kernel<L, ACT>
+
+NORM_CASES = [
+    # ---- GroupNorm forward, one launch (HW <= 256): gn_slab_kernel<MAXCH, GP, 0>; GP groups per block so that a pack is whole 16-byte
+    #      pieces (cpg = C / groups: GP 1 if cpg % 8 == 0, 2 if cpg % 4 == 0, 4 if cpg % 2 == 0); MAXCH from ceil(HW * GP * cpg / 8 / T)
+    _gn("gn_s21_hw250", 3, 250, 256),                            # cpg 8: one piece per row, 250 of 256 threads
+    _gn("gn_s21_hw1", 2, 1, 256, silu=True),                     # a single row: 8 elements per group
+    _gn("gn_s41_hw200", 2, 200, 1280, silu=True),                # 1000 pieces = 3 * 256 + 232: ragged last piece
+    _gn("gn_s81_hw256_cat", 2, 256, 1280, C1=648, silu=True),    # the 16x16 level; the concat split falls inside a group
+    _gn("gn_s161_g8", 2, 256, 2560, groups=8),                   # cpg 320: 10 pieces per thread at 1024 threads
+    _gn("gn_s22_hw64", 3, 64, 640),                              # cpg 20, packs of 2 groups
+    _gn("gn_s22_hw9_cat", 3, 9, 640, C1=328, silu=True),         # 3x3 map; C1 = 8 * 40 + 8 inside a pack
+    _gn("gn_s42_hw200_cat", 2, 200, 640, C1=328, silu=True),
+    _gn("gn_s82_hw256_cat", 2, 256, 1920, C1=1288, silu=True),   # cpg 60; C1 = 10 * 120 + 88 inside a pack
+    _gn("gn_s162_g2_cat", 2, 256, 264, groups=2, C1=136),        # cpg 132: one pack of 33 pieces per row
+    _gn("gn_s24_hw255", 3, 255, 64),                             # cpg 2: a pack of 4 groups is one piece
+    _gn("gn_s24_hw64_cat", 3, 64, 320, C1=168, silu=True),       # cpg 10; C1 = 4 * 40 + 8 inside a pack
+    _gn("gn_s44_hw200_cat", 2, 200, 320, C1=168),
+    _gn("gn_s84_hw256", 3, 256, 320, silu=True, stat=False),     # the product's 16x16 level at 320 channels, no statistics asked
+    _gn("gn_s84_hw256_cat", 2, 256, 960, C1=328, silu=True),     # cpg 30; C1 % 120 != 0
+    _gn("gn_s164_cat", 2, 256, 2112, C1=1064),                   # cpg 66: 33 pieces per row and pack
+    # ---- GroupNorm forward, three launches (HW > 256, or the slab refused): gn_stats_kernel / gn_finalize_kernel / gn_apply_kernel<false>
+    _gn("gn_t_hw257_c320", 3, 257, 320, silu=True),              # 32 rows per chunk: the last chunk has 1 row
+    _gn("gn_t_hw1000_c320_cat8", 3, 1000, 320, C1=8),            # last chunk 8 rows; the first source is one piece wide
+    _gn("gn_t_hw1000_c960_cat", 2, 1000, 960, C1=952, silu=True),  # 240 threads (not whole waves), 16 rows per chunk; the second source is one piece
+    _gn("gn_t_hw257_c64", 3, 257, 64),                           # 8 pieces per row, 32 row slices, one row per thread
+    _gn("gn_t_hw300_c64_g1", 3, 300, 64, groups=1),
+    _gn("gn_t_hw300_c64_g8", 3, 300, 64, groups=8, silu=True),
+    _gn("gn_t_hw260_c4096_g64", 2, 260, 4096, groups=64),        # 512 threads, one row slice, 8 rows per chunk (last: 4)
+    _gn("gn_t_hw200_c8192_g8", 2, 200, 8192, groups=8),          # HW <= 256 but 25 pieces per thread: the slab refuses; 1024 threads
+    # ---- GroupNorm forward from the producers' column statistics: gn_finalize_cs_kernel + apply
+    _gn("gn_cs_hw32_c320", 3, 32, 320, cs=True, silu=True),      # one slab per sample
+    _gn("gn_cs_hw288_c640", 3, 288, 640, cs=True),
+    _gn("gn_cs_hw1024_c320", 3, 1024, 320, cs=True, silu=True),  # the 32x32 level
+    _gn("gn_cs_hw32_c960_cat", 3, 32, 960, C1=640, cs=True),
+    _gn("gn_cs_hw288_c640_cat", 3, 288, 640, C1=328, cs=True, silu=True),   # the split falls inside a group
+    _gn("gn_cs_hw1024_c1920_cat", 3, 1024, 1920, C1=1288, cs=True, silu=True),
+    # ---- GroupNorm backward, one launch (saved statistics, HW <= 256, at most 4 piece pairs per thread): gnb_slab_kernel<MAXCH, GP>
+    _gnb("gnb_s21_hw250", 3, 250, 256, silu=True),
+    _gnb("gnb_s41_hw200_cat", 2, 200, 1280, C1=648, silu=True, acc=3),
+    _gnb("gnb_s41_hw256_c4096", 2, 256, 4096),                   # 4096 pieces = 4 * 1024: the last shape the slab takes
+    _gnb("gnb_s22_hw64_cat", 3, 64, 640, C1=328, acc=1),
+    _gnb("gnb_s42_hw200_cat", 2, 200, 640, C1=328, silu=True),
+    _gnb("gnb_s24_hw64_cat", 3, 64, 320, C1=168, silu=True, acc=2),
+    _gnb("gnb_s44_hw256_cat", 2, 256, 960, C1=328, silu=True, acc=3),
+    # ---- GroupNorm backward, three launches: gnb_partial_kernel / gnb_finalize_kernel / gnb_apply_kernel
+    _gnb("gnb_t_hw256_c4352", 2, 256, 4352),                     # 4352 pieces: 5 per thread, the slab refuses; saved statistics
+    _gnb("gnb_t_saved_hw257_c320", 3, 257, 320, silu=True),
+    _gnb("gnb_t_saved_hw1000_c960_cat", 2, 1000, 960, C1=8, acc=3),
+    _gnb("gnb_t_own_hw257_c320", 3, 257, 320, saved=False, acc=1),             # its own statistics pass (gn_stats + gn_finalize)
+    _gnb("gnb_t_own_hw200_c960_cat", 2, 200, 960, C1=952, silu=True, saved=False, acc=2),
+    _gnb("gnb_t_own_hw1000_c64_g8", 3, 1000, 64, groups=8, saved=False),
+]
+# ---- LayerNorm, L lanes per row x 5 pieces (C = 40 L, parameters 16-byte aligned): M % rows-per-block in {1, rpb - 1}
+for _C, _L in _LN_ROWS.items():
+    _rpb = 4 * 64 // _L
+    NORM_CASES += [dict(id=f"ln_r{_L}_m{2 * _rpb + 1}", op="ln", M=2 * _rpb + 1, C=_C, align=True),
+                   dict(id=f"ln_r{_L}_m{3 * _rpb - 1}", op="ln", M=3 * _rpb - 1, C=_C, align=True)]
+# ---- LayerNorm, one wave per row: layernorm_kernel<1 | 2 | 3 | 8> at both sides of each threshold, and the C = 40 L widths with misaligned parameters
+NORM_CASES += [dict(id=f"ln_k_c{_C}_m{_M}", op="ln", M=_M, C=_C, align=True)
+               for _C, _M in ((8, 5), (512, 1), (520, 5), (1024, 1), (1032, 5), (1536, 1), (1544, 5), (4096, 5))]
+NORM_CASES += [dict(id=f"ln_mis_c{_C}_m{_M}", op="ln", M=_M, C=_C, align=False) for _C, _M in ((320, 5), (640, 5), (1280, 1), (2560, 5))]
+# ---- LayerNorm backward: layernorm_bwd_kernel<1 | 2 | 4> (+ layernorm_param_grad_kernel, M <= 4096)
+NORM_CASES += [dict(id=f"lnb_c{_C}_m{_M}" + ("_p" if _p else "") + ("_acc" if _a else ""), op="lnb", M=_M, C=_C, param=_p, acc=_a)
+               for _C, _M, _p, _a in ((512, 7, True, 0), (512, 4096, True, 0), (520, 1, True, 1), (1024, 7, False, 1), (1032, 7, True, 0),
+                                      (1032, 4096, True, 0), (2048, 1, False, 0), (2048, 4096, False, 1))]
+# ---- LayerNorm with SAM's window partition: 14x14 windows on 20x27 (padding on both axes) and 28x28 (none)
+NORM_CASES += [dict(id=f"lnwin_c{_C}_{_H}x{_W}_mode{_m}", op="lnwin", B=2, H=_H, W=_W, C=_C, ws=14, mode=_m)
+               for _C in _LN_ROWS for (_H, _W) in ((20, 27), (28, 28)) for _m in (1, 2)]
+# ---- narrow LayerNorm (+ GELU): one C per lane count, M = 301 is no multiple of any block's rows
+NORM_CASES += [dict(id=f"lnact_c{_C}" + ("_gelu" if _g else ""), op="lnact", M=301, C=_C, gelu=_g) for _C in _NARROW for _g in (False, True)]
+
+NORM_CASE_IDS = [c["id"] for c in NORM_CASES]
+
+
+# --------------------------------------------------------------------------------------------------- norm.hip: ledger
+def _ids(op, **kw):
+    return [c["id"] for c in NORM_CASES if c["op"] == op and all(c[k] == v for k, v in kw.items())]
+
+
+def _pref(*prefixes):
+    return [i for i in NORM_CASE_IDS if i.startswith(prefixes)]
+
+
+_GN3 = _pref("gn_t_")
+_GNB3 = _pref("gnb_t_")
+NORM_LEDGER = {
+    "gn_slab_kernel<2, 1, 0>": ("default", _pref("gn_s21_")),
+    "gn_slab_kernel<4, 1, 0>": ("default", _pref("gn_s41_")),
+    "gn_slab_kernel<8, 1, 0>": ("default", _pref("gn_s81_")),
+    "gn_slab_kernel<16, 1, 0>": ("default", _pref("gn_s161_")),
+    "gn_slab_kernel<2, 2, 0>": ("default", _pref("gn_s22_")),
+    "gn_slab_kernel<4, 2, 0>": ("default", _pref("gn_s42_")),
+    "gn_slab_kernel<8, 2, 0>": ("default", _pref("gn_s82_")),
+    "gn_slab_kernel<16, 2, 0>": ("default", _pref("gn_s162_")),
+    "gn_slab_kernel<2, 4, 0>": ("default", _pref("gn_s24_")),
+    "gn_slab_kernel<4, 4, 0>": ("default", _pref("gn_s44_")),
+    "gn_slab_kernel<8, 4, 0>": ("default", _pref("gn_s84_")),
+    "gn_slab_kernel<16, 4, 0>": ("default", _pref("gn_s164_")),
+    "gn_stats_kernel": ("default", _GN3 + _pref("gnb_t_own_")),
+    "gn_finalize_kernel": ("default", _GN3 + _pref("gnb_t_own_")),
+    "gn_finalize_cs_kernel": ("default", _pref("gn_cs_")),
+    "gn_apply_kernel<false>": ("default", _GN3 + _pref("gn_cs_")),
+    "gnb_slab_kernel<2, 1>": ("default", _pref("gnb_s21_")),
+    "gnb_slab_kernel<4, 1>": ("default", _pref("gnb_s41_")),
+    "gnb_slab_kernel<2, 2>": ("default", _pref("gnb_s22_")),
+    "gnb_slab_kernel<4, 2>": ("default", _pref("gnb_s42_")),
+    "gnb_slab_kernel<2, 4>": ("default", _pref("gnb_s24_")),
+    "gnb_slab_kernel<4, 4>": ("default", _pref("gnb_s44_")),
+    "gnb_partial_kernel": ("default", _GNB3),
+    "gnb_finalize_kernel": ("default", _GNB3),
+    "gnb_apply_kernel": ("default", _GNB3),
+    "layernorm_kernel<1>": ("default", ["ln_k_c8_m5", "ln_k_c512_m1", "ln_mis_c320_m5"]),
+    "layernorm_kernel<2>": ("default", ["ln_k_c520_m5", "ln_k_c1024_m1", "ln_mis_c640_m5"]),
+    "layernorm_kernel<3>": ("default", ["ln_k_c1032_m5", "ln_k_c1536_m1", "ln_mis_c1280_m1"]),
+    "layernorm_kernel<8>": ("default", ["ln_k_c1544_m5", "ln_k_c4096_m5", "ln_mis_c2560_m5"]),
+    "layernorm_bwd_kernel<1>": ("default", _ids("lnb", C=512)),
+    "layernorm_bwd_kernel<2>": ("default", _ids("lnb", C=520) + _ids("lnb", C=1024)),
+    "layernorm_bwd_kernel<4>": ("default", _ids("lnb", C=1032) + _ids("lnb", C=2048)),
+    "layernorm_param_grad_kernel": ("default", _ids("lnb", param=True)),
+}
+for _C, _L in _LN_ROWS.items():
+    NORM_LEDGER[f"layernorm_rows_kernel<{_L}, 5>"] = ("default", _pref(f"ln_r{_L}_"))
+    for _m in (1, 2):
+        NORM_LEDGER[f"layernorm_window_kernel<{_L}, 5, {_m}>"] = ("default", _ids("lnwin", C=_C, mode=_m))
+for _C, _L in _NARROW.items():
+    for _g in (False, True):
+        NORM_LEDGER[f"layernorm_narrow_kernel<{_L}, {int(_g)}>"] = ("default", _ids("lnact", C=_C, gelu=_g))
+
+
 def expected_kernels(case_id):
     """ledger keys whose `default` row lists this case"""
-    return sorted(k for k, (kind, v) in LEDGER.items() if kind == "default" and case_id in v)
+    return sorted(k for led in (LEDGER, NORM_LEDGER) for k, (kind, v) in led.items() if kind == "default" and case_id in v)

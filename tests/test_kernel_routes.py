@@ -1,6 +1,6 @@
-"""Route ledger of gemm_conv.hip / attention_fast.hip (tests/route_cases.py) and the GPU route cases behind it.
+"""Route ledger of gemm_conv.hip / attention_fast.hip / norm.hip (tests/route_cases.py) and the GPU route cases behind it.
 
-CPU: the set of kernel instantiations the default build compiles — hipcc's device-only LLVM IR of the two sources with the library's flags
+CPU: the set of kernel instantiations the default build compiles — hipcc's device-only LLVM IR of the three sources with the library's flags
 (at -O0: which kernels a translation unit emits does not depend on the optimisation level) — must equal the ledger's keys, in both
 directions, so an instantiation that is added or removed fails here until someone classifies it.
 
@@ -8,6 +8,7 @@ GPU: tools/route_check.py in a fresh child process with every AE_* variable remo
 with AE_ROWPANEL_ANY_M=1, set by test_hip_ops.py): every case must reach its declared instantiations, pass the element-wise float64
 check, leave its guard areas untouched and repeat bit for bit; every `default` ledger row must be reached by each case it lists.  Every
 attention case also carries the log-sum-exp outputs through the same checks and reports their worst error / bound as `lse_ratio`.
+The cases of norm.hip run the same way in a child process of their own (tools/norm_route_check.py, test_norm_route_cases_on_gpu).
 """
 import json
 import os
@@ -22,8 +23,13 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import route_cases as RC  # noqa: E402
 
-FAMILY_RE = re.compile(r"^void (?:\(anonymous namespace\)::)?(gemm_kernel|attn_fast_kernel|attn_pipe_kernel)<([^<>]*)>\(")
-PLAIN = ("splitk_reduce_kernel", "colstats_kernel")
+NORM_FAMILIES = ("gn_slab_kernel", "gn_apply_kernel", "gnb_slab_kernel", "layernorm_rows_kernel", "layernorm_kernel", "layernorm_window_kernel",
+                 "layernorm_narrow_kernel", "layernorm_bwd_kernel")
+FAMILY_RE = re.compile(r"^void (?:\(anonymous namespace\)::)?(gemm_kernel|attn_fast_kernel|attn_pipe_kernel|" + "|".join(NORM_FAMILIES) + r")<([^<>]*)>\(")
+NORM_PLAIN = ("gn_stats_kernel", "gn_finalize_kernel", "gn_finalize_cs_kernel", "gnb_partial_kernel", "gnb_finalize_kernel", "gnb_apply_kernel",
+              "layernorm_param_grad_kernel")
+PLAIN = ("splitk_reduce_kernel", "colstats_kernel") + NORM_PLAIN
+NORM_CHILD_TIMEOUT = 180    # seconds for tools/norm_route_check.py; measured on the MI355X: 12 s for the whole child (8.8 s of cases and sweep)
 
 
 def _kernel_keys(ir_text):
@@ -43,7 +49,7 @@ def compiled_instantiations(tmpdir):
     from anyedit_amd import build as B
     hipcc = B._hipcc()
     keys = []
-    for src in ("gemm_conv.hip", "attention_fast.hip"):
+    for src in ("gemm_conv.hip", "attention_fast.hip", "norm.hip"):
         flags = [("-O0" if f == "-O3" else f) for f in B.FLAGS if f != "-fPIC"] + B.EXTRA.get(src, [])
         out = os.path.join(str(tmpdir), src.replace(".hip", ".ll"))
         subprocess.run([hipcc] + flags + ["--cuda-device-only", "-emit-llvm", "-S", os.path.join(B.CSRC, src), "-o", out], check=True,
@@ -71,13 +77,34 @@ def test_ledger_rows_are_well_formed():
     assert not whole, f"attention rows reached only at Nq % 128 == 0: {whole}"
 
 
+def test_norm_ledger_rows_are_well_formed():
+    ids = set(RC.NORM_CASE_IDS)
+    assert len(ids) == len(RC.NORM_CASES) and not ids & set(RC.CASE_IDS), "duplicate case ids"
+    assert not set(RC.NORM_LEDGER) & set(RC.LEDGER)
+    for key, (kind, what) in RC.NORM_LEDGER.items():
+        assert kind == "default", (key, kind)
+        assert what and all(c in ids for c in what), (key, [c for c in what if c not in ids])
+    for c in RC.NORM_CASES:
+        assert c["op"] in ("gn", "gnb", "ln", "lnb", "lnwin", "lnact"), c
+    listed = {c for kind, what in RC.NORM_LEDGER.values() for c in what}
+    assert not ids - listed, f"cases that assert no route: {sorted(ids - listed)}"
+    # every group pack wider than one group is reached by a concat input whose split falls inside a pack (C1 % (GP * cpg) != 0)
+    byid = {c["id"]: c for c in RC.NORM_CASES}
+    for key, (kind, what) in RC.NORM_LEDGER.items():
+        m = re.match(r"gnb?_slab_kernel<\d+, ([24])\b", key)
+        if m:
+            gp = int(m.group(1))
+            assert any(byid[c]["C1"] and byid[c]["C1"] % (gp * byid[c]["C"] // byid[c]["groups"]) for c in what), f"{key}: no case with a concat split inside a pack"
+
+
 def test_ledger_equals_the_compiled_instantiations(tmp_path):
     keys = compiled_instantiations(tmp_path)
     assert len(keys) == len(set(keys)), "a kernel key appears twice"
+    ledger = set(RC.LEDGER) | set(RC.NORM_LEDGER)
     # (equality with the ledger's own count per family: a regular expression that silently finds nothing cannot pass)
-    for family in ("gemm_kernel<", "attn_"):
-        assert sum(k.startswith(family) for k in keys) == sum(k.startswith(family) for k in RC.LEDGER) > 0, (family, keys)
-    compiled, ledger = set(keys), set(RC.LEDGER)
+    for family in ("gemm_kernel<", "attn_") + tuple(f + "<" for f in NORM_FAMILIES) + NORM_PLAIN:
+        assert sum(k.startswith(family) for k in keys) == sum(k.startswith(family) for k in ledger) > 0, (family, keys)
+    compiled = set(keys)
     assert not compiled - ledger, f"instantiations without a ledger row (classify them in tests/route_cases.py): {sorted(compiled - ledger)}"
     assert not ledger - compiled, f"ledger rows for instantiations the default build no longer compiles: {sorted(ledger - compiled)}"
 
@@ -102,4 +129,32 @@ def test_route_cases_on_gpu():
     no_lse = [i for i in attn if not isinstance(results[i].get("lse_ratio"), float) or not results[i]["lse_ratio"] <= 1.0]
     assert not no_lse, f"attention cases without a checked log-sum-exp: {no_lse}"
     print("lse_ratio per attention case: " + ", ".join(f"{i} {results[i]['lse_ratio']:.3f}" for i in attn))
+    assert p.returncode == 0, p.stderr[-4000:]
+
+
+@pytest.mark.gpu
+def test_norm_route_cases_on_gpu():
+    """norm.hip: every case reaches its rows, passes the statistics and element-wise float64 checks (tests/norm_ref.py), leaves its guards
+    untouched and repeats bit for bit; prints the worst error / bound per case and the conditioning sweep (reported, not asserted)."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("AE_")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "norm_route_check.py")], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=NORM_CHILD_TIMEOUT)
+    print(p.stdout)
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("NORM_ROUTE_SUMMARY ")]
+    assert lines, f"norm_route_check.py ended without a summary (exit {p.returncode}):\n{p.stdout[-4000:]}\n{p.stderr[-4000:]}"
+    summary = json.loads(lines[-1][len("NORM_ROUTE_SUMMARY "):])
+    assert summary["aborted"] is None, f"GPU work stopped at {summary['aborted']}"
+    results = {r["id"]: r for r in summary["results"]}
+    assert set(results) == set(RC.NORM_CASE_IDS), sorted(set(RC.NORM_CASE_IDS) - set(results))
+    failed = {i: r["error"] for i, r in results.items() if not r["ok"]}
+    assert not failed, failed
+    unreached = [(k, c) for k, (kind, cases) in RC.NORM_LEDGER.items() for c in cases if k not in results[c]["keys"]]
+    assert not unreached, unreached
+    assert all(r["guards"] == "intact" and isinstance(r["ratio"], float) and r["ratio"] <= 1.0 for r in results.values())
+    no_stat = [c["id"] for c in RC.NORM_CASES if (c["op"] == "gnb" and c["saved"] or c["op"] == "gn" and c["stat"])
+               and not (isinstance(results[c["id"]]["stat_ratio"], float) and results[c["id"]]["stat_ratio"] <= 1.0)]
+    assert not no_stat, f"GroupNorm cases without checked statistics: {no_stat}"
+    print("worst error / bound per case (output, statistics): " + ", ".join(
+        f"{i} {r['ratio']:.3f}" + (f" {r['stat_ratio']:.3f}" if r["stat_ratio"] is not None else "") for i, r in results.items()))
+    print("conditioning sweep, worst |rstd^/rstd - 1| per route and |mean|/sigma: " + json.dumps(summary["conditioning"]))
     assert p.returncode == 0, p.stderr[-4000:]
