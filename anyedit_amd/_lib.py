@@ -134,6 +134,9 @@ SIGNATURES = {
     "ae_gdino_proposals_f32": [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "ae_gdino_query_sine": [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p],
     "ae_gdino_box_refine_f32": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p],
+    "ae_gdino_text_spans": [c_void_p, c_int, c_int, c_int, c_int] + [c_long] * 8 + [c_void_p, c_void_p, c_void_p, c_void_p],
+    "ae_bert_embed_ln_bf16": [c_void_p, c_void_p, c_void_p] + [c_void_p] * 6 + [c_int] * 6 + [c_float, c_void_p],
+    "ae_attn_span_short_bf16": [c_void_p] * 5 + [c_int] * 4 + [c_long] * 12 + [c_float, c_void_p],
 }
 _RESTYPES = {"ae_last_error": ctypes.c_char_p, "ae_groupnorm_workspace_floats": c_long, "ae_conv3x3_workspace_floats": c_long,
              "ae_groupnorm_bwd_workspace_floats": c_long, "ae_attn_fp8_workspace_bytes": c_long, "ae_attn_bwd_workspace_floats": c_long,

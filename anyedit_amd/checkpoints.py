@@ -335,6 +335,39 @@ def load_groundingdino_transformer(module, path_or_state_dict, location="cpu"):
     return layout
 
 
+def load_groundingdino_text(module, path_or_state_dict, location="cpu"):
+    """Fills a `groundingdino.groundingdino.GroundingDINOText` (`bert.*` + `feat_map.*`) from a file or a state dict.  Recognised forms: a
+    GroundingDINO checkpoint (`torch.load(path)["model"]` or the dict itself) whose `bert.*` and `feat_map.*` entries are read and every other
+    entry ignored; the same with a `module.` prefix in front; a bare BertModel state dict (`embeddings.*`, `encoder.layer.N.*`, `pooler.dense.*`)
+    with `feat_map.*` beside it.  The `embeddings.position_ids` / `embeddings.token_type_ids` buffers of older checkpoints are tolerated.
+    Strict, as `load_groundingdino_encoder`.  Returns the form found."""
+    sd = path_or_state_dict
+    if not isinstance(sd, dict):
+        from anyedit_amd.cldm.model import load_state_dict
+        sd = load_state_dict(sd, location)
+    if isinstance(sd.get("model"), dict):
+        sd = sd["model"]
+    if any(k.startswith("module.bert.") for k in sd):
+        layout = "groundingdino-module"
+        sd = {k[len("module."):]: v for k, v in sd.items() if k.startswith(("module.bert.", "module.feat_map."))}
+    elif any(k.startswith("bert.") for k in sd):
+        layout = "groundingdino"
+        sd = {k: v for k, v in sd.items() if k.startswith(("bert.", "feat_map."))}
+    else:
+        layout = "bert"
+        sd = {(k if k.startswith("feat_map.") else "bert." + k): v for k, v in sd.items()}
+    sd = {k: v for k, v in sd.items() if k not in ("bert.embeddings.position_ids", "bert.embeddings.token_type_ids")}
+    own = module.state_dict()
+    missing = sorted(k for k in own if k not in sd)
+    if missing:
+        raise KeyError(f"load_groundingdino_text: {len(missing)} tensor(s) of the module are not in the checkpoint ({layout} form), first: '{missing[0]}'")
+    unexpected = sorted(k for k in sd if k not in own)
+    if unexpected:
+        raise KeyError(f"load_groundingdino_text: {len(unexpected)} checkpoint tensor(s) have no place in the module ({layout} form), first: '{unexpected[0]}'")
+    module.load_state_dict(sd, strict=True)
+    return layout
+
+
 def load_sd_checkpoint(path, unet=None, vae=None, text_encoder=None, location="cpu"):
     """`load_unet_weights`' sibling for a FULL SD-1.5 state dict (CompVis lineage): routes `model.diffusion_model.*` to `unet`,
     `first_stage_model.*` to `vae` and `cond_stage_model.*` to `text_encoder` (a FrozenCLIPEmbedder); a part given as None is skipped.

@@ -1064,6 +1064,105 @@ def attention_masked_short(q, k, v, mask, B, H, N, D, scale, q_strides, k_stride
     return out
 
 
+# --------------------------------------------------------------------------- GroundingDINO text side (csrc/gdino_text.hip)
+TEXT_SPANS_MAX_N = 256
+BERT_EMBED_MAX_C = 2048
+
+
+def _ids2(t, name):
+    if not t.is_cuda:
+        raise ValueError(f"{name}: expected a GPU tensor (anyedit_amd has no CPU path)")
+    if t.dtype not in (torch.int32, torch.int64) or t.dim() != 2 or not t.is_contiguous():
+        raise TypeError(f"{name}: expected a contiguous int32 / int64 [B, N] tensor, got {t.dtype} {tuple(t.shape)}")
+
+
+def gdino_text_spans(ids, special_ids, spans=None, position_ids=None, dense_mask=None, want_mask=False):
+    """bertwarper.py:180-273 in one launch, no host synchronisation: ids int32 / int64 [B, N] (N <= 256), `special_ids` up to 8 python ints ->
+    (spans int32 [B, N, 2] = the key range [lo, hi) of every query, position_ids int64 [B, N], dense bool [B, N, N] mask or None).  The dense
+    mask is written when `want_mask` or a `dense_mask` buffer (bool / uint8) is given.  CONTRACT: column 0 of every row is a special token."""
+    _ids2(ids, "gdino_text_spans.ids")
+    B, N = ids.shape
+    if not 1 <= N <= TEXT_SPANS_MAX_N:
+        raise ValueError(f"gdino_text_spans: {N} tokens; ae_gdino_text_spans takes between 1 and {TEXT_SPANS_MAX_N}")
+    sp = [int(s) for s in special_ids]
+    if len(sp) > 8:
+        raise ValueError(f"gdino_text_spans: {len(sp)} special ids (at most 8)")
+    dev = ids.device
+    if spans is None:
+        spans = torch.empty(B, N, 2, dtype=torch.int32, device=dev)
+    if position_ids is None:
+        position_ids = torch.empty(B, N, dtype=torch.int64, device=dev)
+    if dense_mask is None and want_mask:
+        dense_mask = torch.empty(B, N, N, dtype=torch.bool, device=dev)
+    _chk(spans, torch.int32, "gdino_text_spans.spans", 3)
+    _chk(position_ids, torch.int64, "gdino_text_spans.position_ids", 2)
+    if tuple(spans.shape) != (B, N, 2) or not spans.is_contiguous() or tuple(position_ids.shape) != (B, N) or not position_ids.is_contiguous():
+        raise ValueError(f"gdino_text_spans: spans must be a contiguous [{B}, {N}, 2] and position_ids a contiguous [{B}, {N}] buffer")
+    if dense_mask is not None:
+        if not dense_mask.is_cuda or dense_mask.dtype not in (torch.bool, torch.uint8) or tuple(dense_mask.shape) != (B, N, N) or not dense_mask.is_contiguous():
+            raise ValueError(f"gdino_text_spans: dense_mask must be a contiguous bool / uint8 [{B}, {N}, {N}] GPU buffer")
+    check(lib.ae_gdino_text_spans(_p(ids), 1 if ids.dtype == torch.int64 else 0, B, N, len(sp), *(sp + [0] * (8 - len(sp))), _p(spans), _p(position_ids),
+                                  _p(dense_mask), _s()), "ae_gdino_text_spans")
+    return spans, position_ids, dense_mask
+
+
+def bert_embed_ln(ids, word, position, token_type, gamma, beta, eps, position_ids=None, type_ids=None, out=None):
+    """BertEmbeddings in one launch: LayerNorm(word[ids] + position[position_ids] + token_type[type_ids]) -> bf16 rows [B*N, C]; the sum is never
+    stored.  ids (and position_ids / type_ids; None = n / row 0) int64 [B, N]; tables bf16, gamma / beta fp32.
+    Indices are NOT read back: one outside its table is clamped into it by the kernel."""
+    _ids2(ids, "bert_embed_ln.ids")
+    B, N = ids.shape
+    for t, n in ((ids, "ids"), (position_ids, "position_ids"), (type_ids, "type_ids")):
+        if t is not None:
+            _ids2(t, "bert_embed_ln." + n)
+            if t.dtype != torch.int64 or tuple(t.shape) != (B, N):
+                raise TypeError(f"bert_embed_ln.{n}: expected int64 [{B}, {N}], got {t.dtype} {tuple(t.shape)}")
+    for t, n in ((word, "word"), (position, "position"), (token_type, "token_type")):
+        _chk(t, BF16, "bert_embed_ln." + n, 2)
+    _chk(gamma, torch.float32, "bert_embed_ln.gamma", 1)
+    _chk(beta, torch.float32, "bert_embed_ln.beta", 1)
+    C = word.shape[1]
+    if C % 8 or C > BERT_EMBED_MAX_C:
+        raise ValueError(f"bert_embed_ln: width {C} must be a multiple of 8 and at most {BERT_EMBED_MAX_C}")
+    if position.shape[1] != C or token_type.shape[1] != C or gamma.numel() != C or beta.numel() != C or \
+            not (word.is_contiguous() and position.is_contiguous() and token_type.is_contiguous() and gamma.is_contiguous() and beta.is_contiguous()):
+        raise ValueError(f"bert_embed_ln: the three tables must be contiguous [rows, {C}] and gamma / beta hold {C} values")
+    if position_ids is None and N > position.shape[0]:
+        raise ValueError(f"bert_embed_ln: {N} tokens, the position table has {position.shape[0]} rows")
+    if out is None:
+        out = torch.empty(B * N, C, dtype=BF16, device=ids.device)
+    _chk(out, BF16, "bert_embed_ln.out", 2)
+    if tuple(out.shape) != (B * N, C) or not out.is_contiguous():
+        raise ValueError(f"bert_embed_ln: out must be a contiguous [{B * N}, {C}] buffer")
+    check(lib.ae_bert_embed_ln_bf16(_p(ids), _p(position_ids), _p(type_ids), _p(word), _p(position), _p(token_type),
+                                    _p(gamma), _p(beta), _p(out), B, N, C, word.shape[0], position.shape[0], token_type.shape[0], float(eps), _s()),
+          "ae_bert_embed_ln_bf16")
+    return out
+
+
+def attention_span_short(q, k, v, spans, B, H, N, D, scale, q_strides, k_strides, v_strides, out=None):
+    """Self-attention over at most 256 tokens under a block-diagonal mask (BERT under GroundingDINO's sub-sentence masks): q/k/v bf16 tensors
+    addressed through (batch, head, row) element strides as in `attention_masked_short`; spans int32 [B, N, 2] contiguous, shared by all heads:
+    query n attends keys [lo, hi); out [B, N, H*D] bf16.  CONTRACT: 0 <= lo < hi <= N.  N in [1, 256], D == 64."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _chk(t, BF16, "attention_span_short." + n)
+    if not 1 <= N <= TEXT_SPANS_MAX_N:
+        raise ValueError(f"attention_span_short: sequence length {N}; ae_attn_span_short_bf16 takes between 1 and {TEXT_SPANS_MAX_N}")
+    if D != 64:
+        raise ValueError(f"attention_span_short: head_dim {D} is not built (supported: 64)")
+    _chk(spans, torch.int32, "attention_span_short.spans", 3)
+    if tuple(spans.shape) != (B, N, 2) or not spans.is_contiguous():
+        raise ValueError(f"attention_span_short: spans must be a contiguous [{B}, {N}, 2] tensor, got {tuple(spans.shape)}")
+    if out is None:
+        out = torch.empty(B, N, H * D, dtype=BF16, device=q.device)
+    _chk(out, BF16, "attention_span_short.out")
+    if out.numel() != B * N * H * D or not out.is_contiguous():
+        raise ValueError(f"attention_span_short: out must be a contiguous [{B}, {N}, {H * D}] buffer")
+    check(lib.ae_attn_span_short_bf16(_p(q), _p(k), _p(v), _p(spans), _p(out), B, H, N, D, *q_strides, *k_strides, *v_strides, N * H * D, D, H * D,
+                                      float(scale), _s()), "ae_attn_span_short_bf16")
+    return out
+
+
 # --------------------------------------------------------------------------- GroundingDINO query selection / decoder (csrc/gdino_decoder.hip)
 CONTRASTIVE_MAX_TEXT = 256
 CONTRASTIVE_MAX_C = 256

@@ -553,6 +553,34 @@ int ae_gdino_query_sine(const float* ref, const float* valid_ratios, float* ref_
 int ae_gdino_box_refine_f32(const float* h, long ldh, const float* w3, const float* b3, const float* ref, float* boxes, float* u_out, long M, int ref_is_logit,
                             void* stream);
 
+/* ---- GroundingDINO's text side (GroundingDINO/groundingdino/models/GroundingDINO/groundingdino.py:233-283; bertwarper.py:180-273; the BertModel the
+ * reference takes from transformers: BertEmbeddings, BertSelfAttention).  Projections are ae_gemm_bf16, the post-LayerNorms ae_layernorm_bf16, the
+ * GELU ae_bias_act_f32_bf16; these are the rest (csrc/gdino_text.hip).  No atomics, no scratch, no host synchronisation; every launch is
+ * deterministic; statistics in fp32, bf16 once at the store.
+ * ae_gdino_text_spans: generate_masks_with_special_tokens / _and_transfer_map (bertwarper.py:180-273) without the host loop or torch.nonzero.  ids
+ *   int32 / int64 [B, N] contiguous; n_special <= 8 special ids s0 .. s7 by value (groundingdino.py:119).  spans int32 [B, N, 2] = (lo, hi): query
+ *   n may attend keys [lo, hi); position_ids int64 [B, N]; dense_mask (may be null) uint8 [B, N, N], 1 = allowed (bertwarper.py:199-215's
+ *   attention_mask).  With e the first special position >= n and p the last special position before e: e exists, e != 0, e != N-1 -> [p+1, e+1),
+ *   position n - (p+1); otherwise [n, n+1), position 0.  Contract (the reference's, which does not reset previous_col per row): column 0 of every
+ *   row is a special token.  1 <= N <= 256, B <= 65535.  One launch.
+ * ae_bert_embed_ln_bf16: BertEmbeddings.forward: out[b*N + n] = LayerNorm(word[ids] + position[position_ids] + token_type[type_ids]), the sum
+ *   kept in fp32 registers and never stored.  ids / position_ids / type_ids int64 [B, N] (what a tokenizer and ae_gdino_text_spans give); position_ids null
+ *   = n, type_ids null = row 0.  Tables bf16 [vocab | positions | types, C] contiguous, gamma / beta fp32 [C], out bf16 [B*N, C].  An index outside its table is
+ *   clamped into it (device ids are not read back).  C % 8 == 0, C <= 2048 (a row lives in one wave's registers), everything 16-byte aligned.
+ * ae_attn_span_short_bf16: BertSelfAttention's core under a block-diagonal mask: out = softmax(scale q k^T over keys [lo, hi)) v.  q/k/v/out bf16
+ *   addressed by (batch, head, row) element strides exactly as ae_attn_masked_short_bf16 (a packed [B*N, 3*H*D] projection is read in place);
+ *   spans int32 [B, N, 2] shared by all heads, contract 0 <= lo < hi <= N (a span outside it is forced inside: it can change a result, never an
+ *   address).  A workgroup stages and multiplies only the 64-key tiles its 64 queries' spans touch; keys outside a query's span have probability
+ *   exactly 0; k / v rows outside every span of a workgroup are never read.  1 <= N <= 256, D == 64, B*H <= 65535; fp32 one-pass softmax.      */
+int ae_gdino_text_spans(const void* ids, int ids_are_i64, int B, int N, int n_special, long s0, long s1, long s2, long s3, long s4, long s5, long s6, long s7,
+                        int* spans, long* position_ids, void* dense_mask, void* stream);
+int ae_bert_embed_ln_bf16(const long* ids, const long* position_ids, const long* type_ids, const void* word_table, const void* position_table,
+                          const void* type_table, const float* gamma, const float* beta, void* out, int B, int N, int C, int vocab, int positions, int types,
+                          float eps, void* stream);
+int ae_attn_span_short_bf16(const void* q, const void* k, const void* v, const int* spans, void* out, int B, int H, int N, int D, long q_sb, long q_sh,
+                            long q_sn, long k_sb, long k_sh, long k_sn, long v_sb, long v_sh, long v_sn, long o_sb, long o_sh, long o_sn, float scale,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
