@@ -137,10 +137,15 @@ SIGNATURES = {
     "ae_gdino_text_spans": [c_void_p, c_int, c_int, c_int, c_int] + [c_long] * 8 + [c_void_p, c_void_p, c_void_p, c_void_p],
     "ae_bert_embed_ln_bf16": [c_void_p, c_void_p, c_void_p] + [c_void_p] * 6 + [c_int] * 6 + [c_float, c_void_p],
     "ae_attn_span_short_bf16": [c_void_p] * 5 + [c_int] * 4 + [c_long] * 12 + [c_float, c_void_p],
+    "ae_gdino_level_geometry": [c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_int, c_void_p],
+    "ae_gdino_neck_groupnorm_workspace_floats": [c_int, c_int],
+    "ae_gdino_neck_groupnorm": [c_void_p, c_long, c_void_p, c_void_p, c_float, c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_void_p],
+    "ae_gdino_ground": [c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
 }
 _RESTYPES = {"ae_last_error": ctypes.c_char_p, "ae_groupnorm_workspace_floats": c_long, "ae_conv3x3_workspace_floats": c_long,
              "ae_groupnorm_bwd_workspace_floats": c_long, "ae_attn_fp8_workspace_bytes": c_long, "ae_attn_bwd_workspace_floats": c_long,
-             "ae_biattn_workspace_bytes": c_long}
+             "ae_biattn_workspace_bytes": c_long, "ae_gdino_neck_groupnorm_workspace_floats": c_long}
 
 
 class AnyEditHipError(RuntimeError):

@@ -368,6 +368,38 @@ def load_groundingdino_text(module, path_or_state_dict, location="cpu"):
     return layout
 
 
+GROUNDINGDINO_TOLERATED = ("bert.embeddings.position_ids", "bert.embeddings.token_type_ids")
+GROUNDINGDINO_TOLERATED_PREFIXES = ("label_enc.",)
+
+
+def load_groundingdino(model, path_or_state_dict, location="cpu"):
+    """Fills a `groundingdino.groundingdino.GroundingDINO` from a file or a state dict: a checkpoint's `{"model": ...}` (groundingdino/util/
+    inference.py:35-36) or the bare state dict, with or without a `module.` prefix on every key.  Strict: every tensor of the model must be in
+    the checkpoint (a shared head under every alias, as PyTorch saves it) and every checkpoint tensor must have a place, except the entries
+    public checkpoints carry and the model does not hold: the buffers `bert.embeddings.position_ids` (and `bert.embeddings.token_type_ids` of
+    newer transformers versions) and the denoising label table `label_enc.*` (a training device; inference never reads it).  The Swin tower's
+    persistent `relative_position_index` buffers are checked against the computed ones by its own load hook.  Returns the form found."""
+    sd = path_or_state_dict
+    if not isinstance(sd, dict):
+        from anyedit_amd.cldm.model import load_state_dict
+        sd = load_state_dict(sd, location)
+    layout = "state_dict"
+    if isinstance(sd.get("model"), dict):
+        sd, layout = sd["model"], "checkpoint"
+    if sd and all(k.startswith("module.") for k in sd):
+        sd, layout = {k[len("module."):]: v for k, v in sd.items()}, layout + "-module"
+    sd = {k: v for k, v in sd.items() if k not in GROUNDINGDINO_TOLERATED and not k.startswith(GROUNDINGDINO_TOLERATED_PREFIXES)}
+    own = model.state_dict()
+    missing = sorted(k for k in own if k not in sd)
+    if missing:
+        raise KeyError(f"load_groundingdino: {len(missing)} tensor(s) of the model are not in the checkpoint ({layout} form), first: '{missing[0]}'")
+    unexpected = sorted(k for k in sd if k not in own)
+    if unexpected:
+        raise KeyError(f"load_groundingdino: {len(unexpected)} checkpoint tensor(s) have no place in the model ({layout} form), first: '{unexpected[0]}'")
+    model.load_state_dict(sd, strict=True)
+    return layout
+
+
 def load_sd_checkpoint(path, unet=None, vae=None, text_encoder=None, location="cpu"):
     """`load_unet_weights`' sibling for a FULL SD-1.5 state dict (CompVis lineage): routes `model.diffusion_model.*` to `unet`,
     `first_stage_model.*` to `vae` and `cond_stage_model.*` to `text_encoder` (a FrozenCLIPEmbedder); a part given as None is skipped.

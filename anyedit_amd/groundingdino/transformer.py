@@ -529,6 +529,17 @@ class Transformer(nn.Module):
             mask_flatten.append(mask.flatten(1))
             pos_flatten.append(p)
         src_flatten, mask_flatten, pos_flatten = torch.cat(src_flatten, 1), torch.cat(mask_flatten, 1).contiguous(), torch.cat(pos_flatten, 1)
+        valid_ratios = torch.stack([self.get_valid_ratio(m) for m in masks], 1)
+        return self.forward_rows(src_flatten, mask_flatten, pos_flatten, sizes, valid_ratios, text_dict, topk_proposals=topk_proposals)
+
+    def forward_rows(self, src_flatten, mask_flatten, pos_flatten, sizes, valid_ratios, text_dict, *, topk_proposals=None):
+        """`forward` behind its flattening (:248-403): src_flatten / pos_flatten [bs, sum(h w), C] (pos_flatten already holds `level_embed`),
+        mask_flatten bool [bs, sum(h w)] with True = padding, sizes a HOST sequence of (h, w) per level, valid_ratios fp32 [bs, levels, 2].  What
+        `ops.gdino_level_geometry` and `ops.gdino_neck_groupnorm` write is taken as it is (bf16 rows are not converted)."""
+        if text_dict is None:
+            raise ValueError("Transformer: text_dict is required (the reference dereferences it unconditionally, :265)")
+        require_inference(self, (self.dropout_rate,))
+        sizes = [(int(h), int(w)) for h, w in sizes]
         dev = src_flatten.device
         spatial_shapes = torch.as_tensor(sizes, dtype=torch.long)                     # on the host: never read back
         key = (tuple(sizes), str(dev))
@@ -536,7 +547,6 @@ class Transformer(nn.Module):
             starts = torch.cat((spatial_shapes.new_zeros((1,)), spatial_shapes.prod(1).cumsum(0)[:-1]))
             self.__dict__["_starts_dev"], self.__dict__["_starts_key"] = starts.to(dev), key
         level_start_index = self.__dict__["_starts_dev"]
-        valid_ratios = torch.stack([self.get_valid_ratio(m) for m in masks], 1)
         memory, memory_text = self.encoder(src_flatten, pos=pos_flatten, level_start_index=level_start_index, spatial_shapes=spatial_shapes,
                                            valid_ratios=valid_ratios, key_padding_mask=mask_flatten, memory_text=text_dict["encoded_text"],
                                            text_attention_mask=~text_dict["text_token_mask"], position_ids=text_dict.get("position_ids"),

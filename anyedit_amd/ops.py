@@ -1333,6 +1333,124 @@ def gdino_box_refine(h, w3, b3, ref, ref_is_logit=False, want_unsigmoid=False, b
     return (boxes, unsigmoid) if want_unsigmoid else boxes
 
 
+def _levels(spatial_shapes, what):
+    shapes = [(int(h), int(w)) for h, w in spatial_shapes]
+    if not 1 <= len(shapes) <= 8 or any(h < 1 or w < 1 for h, w in shapes):
+        raise ValueError(f"{what}: {len(shapes)} levels {shapes} (1 to 8 levels, each at least 1x1)")
+    starts, cur = [], 0
+    for h, w in shapes:
+        starts.append(cur)
+        cur += h * w
+    return shapes, starts, cur
+
+
+def gdino_level_geometry(mask, spatial_shapes, B, temperatureH=20.0, temperatureW=20.0, level_embed=None, device=None, mask_flatten=None,
+                         pos_flatten=None, valid_ratios=None):
+    """Every level's padding mask, sine position embedding and valid ratios in one launch (backbone.py:113 and groundingdino.py:306's nearest
+    resize of the image mask, position_encoding.py:98-131 with normalize=True, transformer.py's `+ level_embed[lvl]` and flatten / cat,
+    Transformer.get_valid_ratio).  mask: bool / uint8 [B, H, W], True = padding, or None (nothing padded; pass `device`); spatial_shapes: a HOST
+    sequence of (h, w) per level; level_embed fp32 [L, 256] or None.  Returns (mask_flatten bool [B, N], pos_flatten bf16 [B, N, 256],
+    valid_ratios fp32 [B, L, 2]) with N = sum h w."""
+    shapes, starts, N = _levels(spatial_shapes, "gdino_level_geometry")
+    L = len(shapes)
+    if mask is not None:
+        if mask.dim() != 3 or mask.shape[0] != B or not mask.is_cuda or mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"gdino_level_geometry: mask must be a GPU bool / uint8 [{B}, H, W] tensor, got {mask.dtype} {tuple(mask.shape)}")
+        mask = _tmp(mask.contiguous())
+        H, W, device = mask.shape[1], mask.shape[2], mask.device
+    else:
+        if device is None:
+            raise ValueError("gdino_level_geometry: pass device= when mask is None")
+        H, W = shapes[0]
+    if level_embed is not None:
+        _chk(level_embed, torch.float32, "gdino_level_geometry.level_embed", 2)
+        if tuple(level_embed.shape) != (L, 256) or not level_embed.is_contiguous():
+            raise ValueError(f"gdino_level_geometry: level_embed must be contiguous [{L}, 256], got {tuple(level_embed.shape)}")
+    if mask_flatten is None:
+        mask_flatten = torch.empty(B, N, dtype=torch.bool, device=device)
+    if pos_flatten is None:
+        pos_flatten = torch.empty(B, N, 256, dtype=BF16, device=device)
+    if valid_ratios is None:
+        valid_ratios = torch.empty(B, L, 2, dtype=torch.float32, device=device)
+    for t, dt, shp, n in ((mask_flatten, torch.bool, (B, N), "mask_flatten"), (pos_flatten, BF16, (B, N, 256), "pos_flatten"),
+                          (valid_ratios, torch.float32, (B, L, 2), "valid_ratios")):
+        _chk(t, dt, "gdino_level_geometry." + n)
+        if tuple(t.shape) != shp or not t.is_contiguous():
+            raise ValueError(f"gdino_level_geometry: {n} must be contiguous {list(shp)}, got {tuple(t.shape)}")
+    c_shapes = (ctypes.c_int * (2 * L))(*[v for hw in shapes for v in hw])
+    c_starts = (ctypes.c_int * L)(*starts)
+    check(lib.ae_gdino_level_geometry(_p(mask), B, H, W, c_shapes, c_starts, L, float(temperatureH), float(temperatureW), _p(level_embed), _p(mask_flatten),
+                                      _p(pos_flatten), _p(valid_ratios), N, _s()), "ae_gdino_level_geometry")
+    return mask_flatten, pos_flatten, valid_ratios
+
+
+NECK_GN_C = 256
+
+
+def gdino_neck_groupnorm_workspace(B, hw, device):
+    return torch.empty(max(1, lib.ae_gdino_neck_groupnorm_workspace_floats(B, hw)), dtype=torch.float32, device=device)
+
+
+def gdino_neck_groupnorm(x, gamma, beta, B, hw, eps=1e-5, out=None, row_offset=0, workspace=None):
+    """GroupNorm(32, 256) of input_proj (groundingdino.py:127-138) on the fp32 projection.  x fp32 [B*hw, 256] (unit inner stride: ops.gemm /
+    ops.conv3x3 with out_f32=True); gamma / beta fp32 [256]; out bf16 [B, N, 256] contiguous with N >= row_offset + hw: sample b's rows go to
+    out[b, row_offset : row_offset + hw] (a level's slice of src_flatten); None = a fresh [B, hw, 256].  Returns out."""
+    _chk(x, torch.float32, "gdino_neck_groupnorm.x", 2)
+    _chk(gamma, torch.float32, "gdino_neck_groupnorm.gamma", 1)
+    _chk(beta, torch.float32, "gdino_neck_groupnorm.beta", 1)
+    if B < 1 or hw < 1 or tuple(x.shape) != (B * hw, NECK_GN_C) or x.stride(1) != 1:
+        raise ValueError(f"gdino_neck_groupnorm: x must be [{B} * {hw}, {NECK_GN_C}] with unit inner stride, got {tuple(x.shape)}")
+    if gamma.numel() != NECK_GN_C or beta.numel() != NECK_GN_C or not gamma.is_contiguous() or not beta.is_contiguous():
+        raise ValueError(f"gdino_neck_groupnorm: gamma and beta must hold {NECK_GN_C} contiguous values")
+    if out is None:
+        out = torch.empty(B, hw, NECK_GN_C, dtype=BF16, device=x.device)
+    _chk(out, BF16, "gdino_neck_groupnorm.out", 3)
+    if out.shape[0] != B or out.shape[2] != NECK_GN_C or not out.is_contiguous() or row_offset < 0 or row_offset + hw > out.shape[1]:
+        raise ValueError(f"gdino_neck_groupnorm: out must be contiguous [{B}, N, {NECK_GN_C}] with N >= {row_offset} + {hw}, got {tuple(out.shape)}")
+    need = lib.ae_gdino_neck_groupnorm_workspace_floats(B, hw)
+    if workspace is None:
+        workspace = _tmp(gdino_neck_groupnorm_workspace(B, hw, x.device))
+    _chk(workspace, torch.float32, "gdino_neck_groupnorm.workspace", 1)
+    if workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError(f"gdino_neck_groupnorm: workspace holds {workspace.numel()} floats, {need} are needed")
+    check(lib.ae_gdino_neck_groupnorm(_p(x), x.stride(0), _p(gamma), _p(beta), float(eps), _p(out), out.stride(0), row_offset, B, hw, _p(workspace), _s()),
+          "ae_gdino_neck_groupnorm")
+    return out
+
+
+GROUND_MAX_QUERIES = 1024
+GROUND_MAX_TEXT = 256
+
+
+def gdino_ground(pred_logits, pred_boxes, box_threshold, text_threshold, out=None):
+    """get_grounding_output's filter (AnyEdit_Collection/adaptive_editing_pipelines/tools/tool.py:125-133) on the GPU.  pred_logits fp32
+    [B, nq, T] (T a multiple of 32, at most 256; -inf on unused columns), pred_boxes fp32 [B, nq, 4].  Returns (count int32 [B], indices int32
+    [B, nq], scores fp32 [B, nq], boxes fp32 [B, nq, 4], token_bits int32 [B, nq, T // 32]): the first count[b] rows hold the queries with
+    max_t sigmoid(logit) > box_threshold in ascending query order; bit t % 32 of word t // 32 says sigmoid(logit_t) > text_threshold.  `out`: the
+    same tuple from an earlier call of the same shape, to be overwritten."""
+    _chk(pred_logits, torch.float32, "gdino_ground.pred_logits", 3)
+    _chk(pred_boxes, torch.float32, "gdino_ground.pred_boxes", 3)
+    B, nq, T = pred_logits.shape
+    if B < 1 or not 1 <= nq <= GROUND_MAX_QUERIES or T % 32 or not 32 <= T <= GROUND_MAX_TEXT or not pred_logits.is_contiguous():
+        raise ValueError(f"gdino_ground: pred_logits must be contiguous [B, nq <= {GROUND_MAX_QUERIES}, T] with T a multiple of 32 up to {GROUND_MAX_TEXT}, "
+                         f"got {tuple(pred_logits.shape)}")
+    if tuple(pred_boxes.shape) != (B, nq, 4) or not pred_boxes.is_contiguous():
+        raise ValueError(f"gdino_ground: pred_boxes must be contiguous [{B}, {nq}, 4], got {tuple(pred_boxes.shape)}")
+    dev = pred_logits.device
+    shapes = ((B,), (B, nq), (B, nq), (B, nq, 4), (B, nq, T // 32))
+    dts = (torch.int32, torch.int32, torch.float32, torch.float32, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dts))
+    for t, s, d in zip(out, shapes, dts):
+        _chk(t, d, "gdino_ground.out")
+        if tuple(t.shape) != s or not t.is_contiguous():
+            raise ValueError(f"gdino_ground: an output must be contiguous {list(s)}, got {tuple(t.shape)}")
+    count, idx, scores, boxes, bits = out
+    check(lib.ae_gdino_ground(_p(pred_logits), _p(pred_boxes), float(box_threshold), float(text_threshold), _p(count), _p(idx), _p(scores), _p(boxes), _p(bits),
+                              B, nq, T, _s()), "ae_gdino_ground")
+    return out
+
+
 def rows_to_nchw_out(x, out):
     """channels-last bf16 rows [B*H*W, C] contiguous -> the given [B, C, H, W] buffer (fp32 or bf16, contiguous): `rows_to_nchw` into a
     buffer the caller owns (no allocation)."""

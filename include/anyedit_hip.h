@@ -581,6 +581,34 @@ int ae_attn_span_short_bf16(const void* q, const void* k, const void* v, const i
                             long q_sn, long k_sb, long k_sh, long k_sn, long v_sb, long v_sh, long v_sn, long o_sb, long o_sh, long o_sn, float scale,
                             void* stream);
 
+/* ---- GroundingDINO's neck and grounded-box filter (csrc/gdino_neck.hip): what joins the Swin stages, the transformer and the caller.  The input_proj
+ * convolutions are ae_gemm_bf16 (1x1) and ae_conv3x3_bf16 (stride 2) with fp32 output.  No atomics, fixed reduction orders: every launch is
+ * deterministic; current stream only, no host synchronisation, no allocation.
+ * ae_gdino_level_geometry: for all L <= 8 levels of a batch in one launch: F.interpolate(m[None].float(), size=...).to(bool) (backbone.py:113,
+ *   groundingdino.py:306), PositionEmbeddingSineHW.forward with normalize=True (position_encoding.py:98-131), the `+ level_embed[lvl]` and the
+ *   flatten / cat of Transformer.forward (transformer.py:226-246) and Transformer.get_valid_ratio.  mask uint8 / bool [B, H, W], non-zero = padding, or
+ *   null (nothing padded); shapes_hw [L][2] = (h, w) and level_start [L] on the host, sum h w == N; level_embed fp32 [L, 256] or null.
+ *   mask_flatten uint8 [B, N]: mask_l[y][x] = mask[y H / h][x W / w] (integer division).  pos_flatten bf16 [B, N, 256]: channels 0..127 from
+ *   y_embed = #{y' <= y : !mask_l[y'][x]}, 128..255 from x_embed = #{x' <= x : !mask_l[y][x']} (true prefix counts: the mask may have holes), each
+ *   e / (e_last + 1e-6) * 2 pi in fp32, channel i of a half = sin (i even) / cos (i odd) of that / T ** (2 (i / 2) / 128), + level_embed in fp32, one
+ *   bf16 rounding.  valid_ratios fp32 [B, L, 2] = (unpadded cells of row 0 / w, of column 0 / h).
+ * ae_gdino_neck_groupnorm: the GroupNorm(32, 256) of input_proj (groundingdino.py:127-138) on the fp32 projection.  x fp32 [B * hw rows] of 256,
+ *   row stride ldx; out bf16: row r of sample b goes to out + b * out_batch_stride + (out_row_offset + r) * 256 (elements) — a level's slice of
+ *   src_flatten [B, N, 256].  Statistics: two-pass per 64-row chunk, chunks combined by mean = sum n_c mean_c / n, M2 = sum (M2_c + n_c (mean_c -
+ *   mean)^2) in a fixed order.  workspace: ae_gdino_neck_groupnorm_workspace_floats(B, hw) floats, written and read inside the call.  Two launches.
+ * ae_gdino_ground: get_grounding_output's filter (AnyEdit_Collection/adaptive_editing_pipelines/tools/tool.py:125-133) per image.  pred_logits fp32
+ *   [B, nq, T] contiguous (-inf on unused columns), T % 32 == 0, T <= 256, nq <= 1024; pred_boxes fp32 [B, nq, 4].  score_q = max_t sigmoid(logit);
+ *   query q is kept when score_q > box_threshold.  count int32 [B]; indices int32 [B, nq], scores fp32 [B, nq], boxes fp32 [B, nq, 4], token_bits
+ *   uint32 [B, nq, T / 32] (bit t % 32 of word t / 32 = sigmoid(logit_t) > text_threshold): rows 0 .. count - 1 hold the kept queries in ascending
+ *   query order, the rows behind them index -1 and zeros.  One launch.                                                                          */
+int ae_gdino_level_geometry(const void* mask, int B, int H, int W, const int* shapes_hw, const int* level_start, int L, float temperatureH,
+                            float temperatureW, const float* level_embed, void* mask_flatten, void* pos_flatten, float* valid_ratios, int N, void* stream);
+long ae_gdino_neck_groupnorm_workspace_floats(int B, int hw);
+int ae_gdino_neck_groupnorm(const float* x, long ldx, const float* gamma, const float* beta, float eps, void* out, long out_batch_stride,
+                            long out_row_offset, int B, int hw, float* workspace, void* stream);
+int ae_gdino_ground(const float* pred_logits, const float* pred_boxes, float box_threshold, float text_threshold, int* count, int* indices, float* scores,
+                    float* boxes, void* token_bits, int B, int nq, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
