@@ -9,39 +9,27 @@
 //   ae_bias_act_f32_bf16        the activation between fc1 and fc2 (CLIPMLP), applied to the fp32 fc1 product + bias and rounded to bf16
 //                               ONCE, after the activation: quick-GELU u * sigmoid(1.702 u) (OpenAI ViT-L/14) or erf-GELU (SD-2's ViT-H).
 //
-// Attention kernel: one 256-thread workgroup per (batch, head).  K and V^T of that head are staged in LDS once (rows >= N are written
-// as zeros, never loaded), each of the 4 waves owns 32 query rows as two 16-row MFMA fragments.  The MFMA operand placement is the
-// one of attention.hip: logits are computed transposed, S^T = K Q^T with v_mfma_f32_16x16x32_bf16, so a lane holds logits of ONE query
-// row and the exponentiated P registers are already the B operand of O^T = V^T P^T (V is transposed while it is written to LDS, key
-// index permuted per 64-key tile so a lane's 8 contraction slots are one 16-byte read).  A whole row (<= 128 keys = 8 key fragments)
-// lives in registers, so the softmax is one pass: row maximum, exp2 with scale * log2(e) folded in, sum, normalise — no online rescale.
-// 16-key fragments wholly above the diagonal of a query fragment are skipped (wave-uniform), not computed and masked; inside the
-// diagonal fragment masked logits take the file-wide finite -1e30 (-ffinite-math-only) and their probability is forced to 0.
-#include "common.hpp"
+// Attention kernel: one 256-thread workgroup per (batch, head), built from the pieces of attn_short.hpp (operand placement, staging, one-pass
+// softmax, PV, store).  Particular to it: K and V^T of the head are staged once in two LDS buffers behind ONE barrier (a whole row is <= 128
+// keys = 8 key fragments), each of the 4 waves owns 32 query rows as two 16-row MFMA fragments, and 16-key fragments wholly above the
+// diagonal of a query fragment are skipped (wave-uniform), not computed and masked; inside the diagonal fragment masked logits take the
+// file-wide finite -1e30 (-ffinite-math-only) and their probability is forced to 0.
+#include "attn_short.hpp"
 
 namespace {
 
 constexpr int NMAX = 128;  // longest sequence: 8 key fragments of 16 in registers per query fragment
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float NEG_BIG = -1.0e30f;
 
-struct CausalArgs {
-    const bf16_t* q; const bf16_t* k; const bf16_t* v; bf16_t* o;
-    int B, H, N;
-    long q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, o_sb, o_sh, o_sn;
-    float scale;
+struct BelowDiagonal {  // the live keys of query row qrow among the nlive fragments that were computed
+    int nlive, qrow, lg;
+    __device__ __forceinline__ bool operator()(int kf, int r, float) const { return kf < nlive && kf * 16 + lg * 4 + r <= qrow; }
 };
 
-__device__ __forceinline__ int vt_pos(int key) {  // inside one 64-key tile: key = 16 f + 4 g + r  ->  16 g + 4 f + r
-    return ((key >> 2) & 3) * 16 + (key >> 4) * 4 + (key & 3);
-}
-
 template <int D>
-__global__ __launch_bounds__(256) void attn_causal_short_kernel(const CausalArgs p) {
+__global__ __launch_bounds__(256) void attn_causal_short_kernel(const ShortAttnArgs p) {
     constexpr int NT = 256;
     constexpr int NC = D / 32;      // K = 32 MFMAs per (key fragment, query fragment)
     constexpr int NDF = D / 16;     // 16-row fragments of O^T
-    constexpr int DCH = D / 8;      // 16-byte chunks per row
     constexpr int KROW = D + 8;     // LDS row strides (elements), +16 B pad
     constexpr int VROW = NMAX + 8;
     static_assert(D == 32 || D == 64, "head_dim 32 or 64");
@@ -54,34 +42,12 @@ __global__ __launch_bounds__(256) void attn_causal_short_kernel(const CausalArgs
     const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
     const int N = p.N;
     const bf16_t* qp = p.q + (long)b * p.q_sb + (long)h * p.q_sh;
-    const bf16_t* kp = p.k + (long)b * p.k_sb + (long)h * p.k_sh;
-    const bf16_t* vp = p.v + (long)b * p.v_sb + (long)h * p.v_sh;
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
 
     // ---- stage K rows and V^T columns [0, NS), NS = N rounded up to 32 (one PV MFMA contracts 32 keys): keys >= N are ZEROS, written,
     // not loaded — their probability is 0, and 0 * (whatever LDS held) must stay 0
     const int NS = (N + 31) & ~31;
-    for (int id = tid; id < NS * DCH; id += NT) {
-        const int key = id / DCH, c = id - key * DCH;
-        const u32x4 t = key < N ? *reinterpret_cast<const u32x4*>(kp + (long)key * p.k_sn + c * 8) : zero4;
-        *reinterpret_cast<u32x4*>(sK + key * KROW + c * 8) = t;
-    }
-    for (int id = tid; id < (NS / 2) * DCH; id += NT) {
-        const int pr = id / DCH, c = id - pr * DCH;
-        const int key = 2 * pr;
-        const u32x4 t0 = key < N ? *reinterpret_cast<const u32x4*>(vp + (long)key * p.v_sn + c * 8) : zero4;
-        const u32x4 t1 = key + 1 < N ? *reinterpret_cast<const u32x4*>(vp + (long)(key + 1) * p.v_sn + c * 8) : zero4;
-        const int pos = (key & ~63) + vt_pos(key & 63);  // even; key + 1 lands at pos + 1
-        const uint32_t a0[4] = {t0.x, t0.y, t0.z, t0.w};
-        const uint32_t a1[4] = {t1.x, t1.y, t1.z, t1.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const uint32_t lo = __builtin_amdgcn_perm(a1[e], a0[e], 0x05040100u);  // {a0.lo16, a1.lo16}: d = 8c + 2e
-            const uint32_t hi = __builtin_amdgcn_perm(a1[e], a0[e], 0x07060302u);  // {a0.hi16, a1.hi16}: d = 8c + 2e + 1
-            *reinterpret_cast<uint32_t*>(sVt + (c * 8 + 2 * e) * VROW + pos) = lo;
-            *reinterpret_cast<uint32_t*>(sVt + (c * 8 + 2 * e + 1) * VROW + pos) = hi;
-        }
-    }
+    stage_k_rows<D, NT>(sK, NS, tid, RangeRows{p.k + (long)b * p.k_sb + (long)h * p.k_sh, p.k_sn, 0, 0, N});
+    stage_vt<D, NT>(sVt, VROW, NS, tid, RangeRows{p.v + (long)b * p.v_sb + (long)h * p.v_sh, p.v_sn, 0, 0, N});
     __syncthreads();  // the only barrier: nothing below writes LDS
 
     const int q0 = wave * 32;
@@ -97,26 +63,16 @@ __global__ __launch_bounds__(256) void attn_causal_short_kernel(const CausalArgs
         const int qrow = qa0 + l15;
         const int nlive = min(qa0 / 16 + 1, nfrag);  // key fragments at or below the diagonal of this query fragment
 
-        // Q fragment (B operand of S^T = K Q^T): lane (q = l15, g) holds Q[q][32c + 8g .. +8]; rows >= N clamped into range (never stored)
         bf16x8_t qf[NC];
-        {
-            const bf16_t* qr = qp + (long)min(qrow, N - 1) * p.q_sn;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) qf[c] = as_bf16x8(*reinterpret_cast<const u32x4*>(qr + c * 32 + lg * 8));
-        }
+        load_q_frag(qf, qp + (long)min(qrow, N - 1) * p.q_sn, lg);
 
-        // ---- S^T = K Q^T: lane holds S^T[key = 16 kf + 4 g + r][q = l15], in the exp2 domain, masked above the diagonal
+        // ---- S^T = K Q^T in the exp2 domain, masked above the diagonal
         f32x4 s[8];
         float mx = NEG_BIG;
 #pragma unroll
         for (int kf = 0; kf < 8; ++kf) {
             if (kf < nlive) {
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    const bf16x8_t kfr = as_bf16x8(*reinterpret_cast<const u32x4*>(sK + (kf * 16 + l15) * KROW + c * 32 + lg * 8));
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr, qf[c], acc, 0, 0, 0);
-                }
+                const f32x4 acc = logit_frag(sK, kf, qf, l15, lg);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int key = kf * 16 + lg * 4 + r;
@@ -128,53 +84,19 @@ __global__ __launch_bounds__(256) void attn_causal_short_kernel(const CausalArgs
                 s[kf] = (f32x4){NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG};
             }
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // key 0 is live for every row: mx is a real logit
-
-        // ---- one-pass softmax: the whole row is in registers
+        mx = query_max(mx);  // key 0 is live for every row: mx is a real logit
         float rs = 0.f;
 #pragma unroll
-        for (int kf = 0; kf < 8; ++kf)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int key = kf * 16 + lg * 4 + r;
-                const float e = (kf < nlive && key <= qrow) ? __builtin_amdgcn_exp2f(s[kf][r] - mx) : 0.f;
-                s[kf][r] = e;
-                rs += e;
-            }
-        rs += __shfl_xor(rs, 16, 64);
-        rs += __shfl_xor(rs, 32, 64);
-        const float inv = 1.0f / rs;  // rs >= 1: the row maximum contributes exp2(0)
+        for (int kf = 0; kf < 8; ++kf) s[kf] = exp_frag(s[kf], kf, mx, rs, BelowDiagonal{nlive, qrow, lg});
+        const float inv = 1.0f / query_sum(rs);
 
-        // ---- O^T = V^T P^T: lane holds O^T[d = 16 df + 4 g + r][q = l15]; P as bf16, 32 keys (two fragments) per MFMA
         f32x4 o[NDF];
 #pragma unroll
         for (int df = 0; df < NDF; ++df) o[df] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (2 * j < nlive) {
-                u32x4 w;
-                w.x = pack_bf16x2(s[2 * j][0], s[2 * j][1]);
-                w.y = pack_bf16x2(s[2 * j][2], s[2 * j][3]);
-                w.z = pack_bf16x2(s[2 * j + 1][0], s[2 * j + 1][1]);
-                w.w = pack_bf16x2(s[2 * j + 1][2], s[2 * j + 1][3]);
-                const bf16x8_t pb = as_bf16x8(w);
-#pragma unroll
-                for (int df = 0; df < NDF; ++df) {
-                    const bf16x8_t vf = as_bf16x8(*reinterpret_cast<const u32x4*>(sVt + (df * 16 + l15) * VROW + (j >> 1) * 64 + lg * 16 + (j & 1) * 8));
-                    o[df] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb, o[df], 0, 0, 0);
-                }
-            }
-        }
-
-        // ---- normalise and store: 4 consecutive d per lane -> 8-byte stores; rows >= N are never stored
-        if (qrow < N) {
-#pragma unroll
-            for (int df = 0; df < NDF; ++df) {
-                u32x2* dst = reinterpret_cast<u32x2*>(op + (long)qrow * p.o_sn + df * 16 + lg * 4);
-                *dst = (u32x2){pack_bf16x2(o[df][0] * inv, o[df][1] * inv), pack_bf16x2(o[df][2] * inv, o[df][3] * inv)};
-            }
-        }
+        for (int j = 0; j < 4; ++j)
+            if (2 * j < nlive) pv_step(o, s[2 * j], s[2 * j + 1], sVt, VROW, pv_col(j, lg), l15);
+        if (qrow < N) store_o_row(op + (long)qrow * p.o_sn, o, inv, lg);  // rows >= N are never stored
     }
 }
 
@@ -246,23 +168,10 @@ __global__ __launch_bounds__(256) void bias_act_kernel(const float* __restrict__
 extern "C" int ae_attn_causal_short_bf16(const void* q, const void* k, const void* v, void* out, int B, int H, int N, int D,
                                          long q_sb, long q_sh, long q_sn, long k_sb, long k_sh, long k_sn,
                                          long v_sb, long v_sh, long v_sn, long o_sb, long o_sh, long o_sn, float scale, void* stream) {
-    AE_REQUIRE(q && k && v && out, "ae_attn_causal_short_bf16: null pointer");
-    AE_REQUIRE(B > 0 && H > 0 && (long)B * H < (1L << 31), "ae_attn_causal_short_bf16: bad sizes B=%d H=%d", B, H);
-    AE_REQUIRE(N >= 1 && N <= NMAX, "ae_attn_causal_short_bf16: sequence length %d outside [1, %d] (a whole row of keys lives in registers)", N, NMAX);
-    AE_REQUIRE(D == 32 || D == 64, "ae_attn_causal_short_bf16: unsupported head_dim %d (supported: 32, 64)", D);
-    AE_REQUIRE((q_sb | q_sh | q_sn | k_sb | k_sh | k_sn | v_sb | v_sh | v_sn) % 8 == 0 && (o_sb | o_sh | o_sn) % 4 == 0,
-               "ae_attn_causal_short_bf16: strides must keep q/k/v rows 16-byte aligned and out rows 8-byte aligned");
-    AE_REQUIRE(q_sb >= 0 && q_sh >= 0 && q_sn >= 0 && k_sb >= 0 && k_sh >= 0 && k_sn >= 0 && v_sb >= 0 && v_sh >= 0 && v_sn >= 0 && o_sb >= 0 && o_sh >= 0 && o_sn >= D,
-               "ae_attn_causal_short_bf16: negative stride, or output rows that overlap");
-    AE_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)out & 7) == 0,
-               "ae_attn_causal_short_bf16: q/k/v must be 16-byte aligned, out 8-byte aligned");
-    AE_REQUIRE(scale > 0.f, "ae_attn_causal_short_bf16: scale must be positive");
-    CausalArgs a{};
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)out;
-    a.B = B; a.H = H; a.N = N;
-    a.q_sb = q_sb; a.q_sh = q_sh; a.q_sn = q_sn; a.k_sb = k_sb; a.k_sh = k_sh; a.k_sn = k_sn;
-    a.v_sb = v_sb; a.v_sh = v_sh; a.v_sn = v_sn; a.o_sb = o_sb; a.o_sh = o_sh; a.o_sn = o_sn;
-    a.scale = scale;
+    static const ShortAttnRules rules{"ae_attn_causal_short_bf16", (1L << 31) - 1, NMAX, "a whole row of keys lives in registers", true, 0,
+                                      "q/k/v must be 16-byte aligned, out 8-byte aligned"};
+    ShortAttnArgs a{};
+    if (const int e = short_attn_args(a, rules, q, k, v, nullptr, out, B, H, N, D, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, o_sb, o_sh, o_sn, scale)) return e;
     const dim3 grid((unsigned)(B * H)), block(256);
     if (D == 32) hipLaunchKernelGGL((attn_causal_short_kernel<32>), grid, block, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((attn_causal_short_kernel<64>), grid, block, 0, (hipStream_t)stream, a);

@@ -12,57 +12,10 @@
 //
 // All three are bandwidth-bound row kernels: fp32 statistics (two passes over registers: mean, then centred variance), one rounding to
 // bf16 at the 16-byte store, no scratch, no atomics.  The two LayerNorm kernels give one wave to a row and a lane up to LN_MAXCH chunks
-// of 8 channels: C <= LN_CMAX = 2048 (ViT-H 1280, ViT-bigG 1664), refused above.
-#include "common.hpp"
+// of 8 channels (wave_ln_store, rowwave.hpp): C <= LN_CMAX = 2048 (ViT-H 1280, ViT-bigG 1664), refused above.
+#include "rowwave.hpp"
 
 namespace {
-
-constexpr int LN_MAXCH = 4;                    // 8-channel chunks per lane
-constexpr int LN_CMAX = 64 * 8 * LN_MAXCH;     // 2048
-
-struct f32x8 { float v[8]; };
-
-__device__ __forceinline__ f32x8 load8_f32(const float* p) {  // 16-byte aligned
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p);
-    const f32x4 b = *reinterpret_cast<const f32x4*>(p + 4);
-    return f32x8{{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}};
-}
-
-// LayerNorm of one row held by a wave as x[i] = channels [8 (lane + 64 i), +8), and its bf16 store
-__device__ __forceinline__ void wave_ln_store(const f32x8 (&x)[LN_MAXCH], int lane, int ncc, int C, const float* __restrict__ gamma,
-                                              const float* __restrict__ beta, float eps, bf16_t* __restrict__ y) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAXCH; ++i)
-        if (lane + i * 64 < ncc) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s += x[i].v[e];
-        }
-    const float mu = wave_reduce_sum(s) / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAXCH; ++i)
-        if (lane + i * 64 < ncc) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float d = x[i].v[e] - mu;
-                q += d * d;
-            }
-        }
-    const float rstd = rsqrtf(wave_reduce_sum(q) / (float)C + eps);
-#pragma unroll
-    for (int i = 0; i < LN_MAXCH; ++i) {
-        const int cc = lane + i * 64;
-        if (cc < ncc) {
-            const f32x8 g = load8_f32(gamma + cc * 8), b = load8_f32(beta + cc * 8);
-            float r[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) r[e] = (x[i].v[e] - mu) * rstd * g.v[e] + b.v[e];
-            *reinterpret_cast<u32x4*>(y + cc * 8) =
-                (u32x4){pack_bf16x2(r[0], r[1]), pack_bf16x2(r[2], r[3]), pack_bf16x2(r[4], r[5]), pack_bf16x2(r[6], r[7])};
-        }
-    }
-}
 
 // one wave per token row (b, n): n = 0 the class token, n = 1 + i patch i of sample b
 __global__ __launch_bounds__(256) void vision_embed_ln_kernel(const float* __restrict__ patch, long ldp, const float* __restrict__ cls,

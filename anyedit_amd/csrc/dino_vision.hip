@@ -14,21 +14,9 @@
 // no scratch, no atomics.  The gate is fp32 arithmetic (every step is relatively accurate); the three-term sum of the embedding can cancel, so
 // it is taken in fp64 (53 bits hold the sum of three fp32 values of like magnitude exactly) and rounded to fp32 once: an fp32 sum would carry
 // the error of its first addition, relative to |patch + bias|, into a result that may be orders of magnitude smaller.
-#include "common.hpp"
+#include "rowwave.hpp"
 
 namespace {
-
-struct f32x8 { float v[8]; };
-
-__device__ __forceinline__ f32x8 load8_f32(const float* p) {  // 16-byte aligned
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p);
-    const f32x4 b = *reinterpret_cast<const f32x4*>(p + 4);
-    return f32x8{{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}};
-}
-
-__device__ __forceinline__ void store8_bf16(bf16_t* p, const float (&r)[8]) {  // 16-byte aligned
-    *reinterpret_cast<u32x4*>(p) = (u32x4){pack_bf16x2(r[0], r[1]), pack_bf16x2(r[2], r[3]), pack_bf16x2(r[4], r[5]), pack_bf16x2(r[6], r[7])};
-}
 
 // one thread per (token row, 8-channel chunk): row = b (G + 1) + n, n = 0 the class token, n = 1 + i patch i of sample b
 __global__ __launch_bounds__(256) void dino_embed_kernel(const float* __restrict__ patch, long ldp, const float* __restrict__ patch_bias,

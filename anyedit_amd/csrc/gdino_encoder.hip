@@ -16,41 +16,22 @@
 // One 256-thread workgroup owns 64 query rows (one 16-row MFMA fragment per wave) of one (sample, head) and walks a range of keys in chunks of
 // BI_CHUNK = 64.  A chunk's key rows (64 x 256 bf16) and then its values, transposed (256 x 64), pass through ONE LDS buffer of 36 KB one after
 // the other — K and V of a head at 256 x 256 are 128 KB each and do not fit beside each other, so they are streamed in key chunks and three
-// workgroups (150 registers: three waves per SIMD) share a CU to cover each other's staging.  Operand placement is the one of swin.hip /
-// clip_text.hip: S^T = K Q^T with v_mfma_f32_16x16x32_bf16 (8 K steps for head_dim 256), a lane holds the logits of ONE query row, the running maximum / sum live in that
-// lane (online softmax in the exp2 domain, each softmax subtracts its own running maximum), and the exponentiated registers are the B operand
-// of O^T = V^T P^T.  The image direction walks all (<= 256) text keys in one workgroup and stores bf16.  The text direction has few queries and
-// very many keys: its key range is cut into at most BI_MAX_SPLIT partials of whole chunks (ae_biattn_split_rows); every partial writes its
-// running maximum, its sum and its un-normalised fp32 accumulator to the workspace, and a combine kernel merges them IN PARTIAL ORDER — no
+// workgroups (150 registers: three waves per SIMD) share a CU to cover each other's staging.  Operand placement, staging, the logit fragment
+// and the PV step are those of attn_short.hpp (8 K steps for head_dim 256); a row does not fit in registers here, so the running maximum / sum
+// live in the lane (online softmax in the exp2 domain, each softmax subtracts its own running maximum).  The image direction walks all
+// (<= 256) text keys in one workgroup and stores bf16.  The text direction has few queries and very many keys: its key range
+// is cut into at most BI_MAX_SPLIT partials of whole chunks (ae_biattn_split_rows); every partial writes its running maximum, its sum and its un-normalised fp32 accumulator to the workspace, and a combine kernel merges them IN PARTIAL ORDER — no
 // floating-point atomics, so two launches on the same inputs are bit-identical.  The workspace is bounded by BI_MAX_SPLIT * Nt * 258 floats per
 // (sample, head): nothing grows with Nv * Nt.
 //
 // Left out on purpose (fuse_modules.py:181-202): the subtraction of the global attn_weights.max() and both clamps to +-50000.  A softmax is
 // invariant to a shift of its row, so the global maximum changes a result only through the clamps, and those act only when the logits of one
 // call span more than 50000.
-#include "common.hpp"
+//
+// Masked short attention is attn_masked_short_kernel (attn_short.hpp) under the ByteMask policy of this file: the window is all of [0, N).
+#include "attn_short.hpp"
 
 namespace {
-
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float NEG_BIG = -1.0e30f;
-
-__device__ __forceinline__ int vt_pos(int key) {  // inside one 64-key tile: key = 16 f + 4 g + r  ->  16 g + 4 f + r
-    return ((key >> 2) & 3) * 16 + (key >> 4) * 4 + (key & 3);
-}
-
-// two value rows (16 bytes each, d = 8c .. 8c+7 of keys `key`, `key + 1`, key even) -> V^T rows d, columns vt_pos(key), vt_pos(key) + 1
-__device__ __forceinline__ void store_vt_pair(bf16_t* sVt, int vrow, int c, int pos, u32x4 t0, u32x4 t1) {
-    const uint32_t a0[4] = {t0.x, t0.y, t0.z, t0.w};
-    const uint32_t a1[4] = {t1.x, t1.y, t1.z, t1.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const uint32_t lo = __builtin_amdgcn_perm(a1[e], a0[e], 0x05040100u);  // {a0.lo16, a1.lo16}: d = 8c + 2e
-        const uint32_t hi = __builtin_amdgcn_perm(a1[e], a0[e], 0x07060302u);  // {a0.hi16, a1.hi16}: d = 8c + 2e + 1
-        *reinterpret_cast<uint32_t*>(sVt + (c * 8 + 2 * e) * vrow + pos) = lo;
-        *reinterpret_cast<uint32_t*>(sVt + (c * 8 + 2 * e + 1) * vrow + pos) = hi;
-    }
-}
 
 // ------------------------------------------------------------------------------------------------------------------ bi-attention
 constexpr int BI_D = 256;          // head_dim of the fusion attention (embed_dim 1024 / 4 heads)
@@ -85,7 +66,6 @@ __global__ __launch_bounds__(256, 2) void biattn_kernel(const BiArgs p) {
     constexpr int D = BI_D;
     constexpr int NC = D / 32;               // K = 32 MFMA steps per logit fragment
     constexpr int NDF = D / 16;              // 16-row fragments of O^T
-    constexpr int DCH = D / 8;               // 16-byte chunks per row
     constexpr int KROW = D + 8;              // LDS row strides (elements), +16 B pad
     constexpr int VROW = BI_CHUNK + 8;
     constexpr int BUF = (BI_CHUNK * KROW > D * VROW) ? BI_CHUNK * KROW : D * VROW;
@@ -102,19 +82,13 @@ __global__ __launch_bounds__(256, 2) void biattn_kernel(const BiArgs p) {
     const int qrow = q0 + l15;
     const int k_begin = split * p.split_rows;
     const int k_end = min(p.Nk, k_begin + p.split_rows);
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
 
     const bf16_t* kbase = p.k + (long)b * p.Nk * p.ldk + h * D;
     const bf16_t* vbase = p.v + (long)b * p.Nk * p.ldv + h * D;
     const uint8_t* mbase = p.kmask ? p.kmask + (long)b * p.Nk : nullptr;
 
-    // Q fragment (B operand of S^T = K Q^T): lane (q = l15, g) holds Q[q][32c + 8g .. +8]; rows >= Nq clamped into range (never stored)
-    bf16x8_t qf[NC];
-    {
-        const bf16_t* qr = p.q + ((long)b * p.Nq + min(qrow, p.Nq - 1)) * p.ldq + h * D;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) qf[c] = as_bf16x8(*reinterpret_cast<const u32x4*>(qr + c * 32 + lg * 8));
-    }
+    bf16x8_t qf[NC];   // rows >= Nq clamped into range (never stored)
+    load_q_frag(qf, p.q + ((long)b * p.Nq + min(qrow, p.Nq - 1)) * p.ldq + h * D, lg);
 
     f32x4 o[NDF];
 #pragma unroll
@@ -125,11 +99,7 @@ __global__ __launch_bounds__(256, 2) void biattn_kernel(const BiArgs p) {
         const int nkf = min(BI_CHUNK / 16, (k_end - c0 + 15) >> 4);   // key fragments of this chunk that hold a key
         __syncthreads();   // the previous chunk's V^T has been read
         // ---- stage K rows of keys [c0, c0 + 64): a key past k_end is zeros, written, never loaded
-        for (int id = tid; id < BI_CHUNK * DCH; id += NT) {
-            const int key = id / DCH, c = id - key * DCH;
-            const u32x4 t = c0 + key < k_end ? *reinterpret_cast<const u32x4*>(kbase + (long)(c0 + key) * p.ldk + c * 8) : zero4;
-            *reinterpret_cast<u32x4*>(sBuf + key * KROW + c * 8) = t;
-        }
+        stage_k_rows<D, NT>(sBuf, BI_CHUNK, tid, RangeRows{kbase, p.ldk, c0, 0, k_end});
         if (tid < BI_CHUNK) sLive[tid] = (c0 + tid < k_end && !(mbase && mbase[c0 + tid])) ? 1 : 0;
         __syncthreads();
 
@@ -140,12 +110,7 @@ __global__ __launch_bounds__(256, 2) void biattn_kernel(const BiArgs p) {
 #pragma unroll
             for (int kf = 0; kf < BI_CHUNK / 16; ++kf) {
                 if (kf < nkf) {
-                    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) {
-                        const bf16x8_t kfr = as_bf16x8(*reinterpret_cast<const u32x4*>(sBuf + (kf * 16 + l15) * KROW + c * 32 + lg * 8));
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr, qf[c], acc, 0, 0, 0);
-                    }
+                    const f32x4 acc = logit_frag(sBuf, kf, qf, l15, lg);
                     const uint32_t live = *reinterpret_cast<const uint32_t*>(sLive + kf * 16 + lg * 4);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -179,33 +144,14 @@ __global__ __launch_bounds__(256, 2) void biattn_kernel(const BiArgs p) {
         __syncthreads();   // every wave has read the K rows
 
         // ---- stage V^T of the same keys into the same buffer (key index permuted inside the 64-key tile: a lane's 8 contraction slots are 16 bytes)
-        for (int id = tid; id < (BI_CHUNK / 2) * DCH; id += NT) {
-            const int pr = id / DCH, c = id - pr * DCH;
-            const int key = 2 * pr;
-            const u32x4 t0 = c0 + key < k_end ? *reinterpret_cast<const u32x4*>(vbase + (long)(c0 + key) * p.ldv + c * 8) : zero4;
-            const u32x4 t1 = c0 + key + 1 < k_end ? *reinterpret_cast<const u32x4*>(vbase + (long)(c0 + key + 1) * p.ldv + c * 8) : zero4;
-            store_vt_pair(sBuf, VROW, c, vt_pos(key), t0, t1);
-        }
+        stage_vt<D, NT>(sBuf, VROW, BI_CHUNK, tid, RangeRows{vbase, p.ldv, c0, 0, k_end});
         __syncthreads();
 
         // ---- O^T += V^T P^T: lane holds O^T[d = 16 df + 4 g + r][q = l15]; P as bf16, 32 keys (two fragments) per MFMA
         if (active) {
 #pragma unroll
-            for (int j = 0; j < BI_CHUNK / 32; ++j) {
-                if (2 * j < nkf) {
-                    u32x4 pw;
-                    pw.x = pack_bf16x2(s[2 * j][0], s[2 * j][1]);
-                    pw.y = pack_bf16x2(s[2 * j][2], s[2 * j][3]);
-                    pw.z = pack_bf16x2(s[2 * j + 1][0], s[2 * j + 1][1]);
-                    pw.w = pack_bf16x2(s[2 * j + 1][2], s[2 * j + 1][3]);
-                    const bf16x8_t pb = as_bf16x8(pw);
-#pragma unroll
-                    for (int df = 0; df < NDF; ++df) {
-                        const bf16x8_t vf = as_bf16x8(*reinterpret_cast<const u32x4*>(sBuf + (df * 16 + l15) * VROW + lg * 16 + j * 8));
-                        o[df] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb, o[df], 0, 0, 0);
-                    }
-                }
-            }
+            for (int j = 0; j < BI_CHUNK / 32; ++j)
+                if (2 * j < nkf) pv_step(o, s[2 * j], s[2 * j + 1], sBuf, VROW, pv_col(j, lg), l15);
         }
     }
 
@@ -220,11 +166,7 @@ __global__ __launch_bounds__(256, 2) void biattn_kernel(const BiArgs p) {
         }
         if (lg == 0) *reinterpret_cast<f32x2*>(w + BI_D) = (f32x2){m_run, l_run};
     } else {
-        const float inv = 1.0f / l_run;   // contract: at least one live key per sample
-        bf16_t* dst = p.out + ((long)b * p.Nq + qrow) * p.ldo + h * D;
-#pragma unroll
-        for (int df = 0; df < NDF; ++df)
-            *reinterpret_cast<u32x2*>(dst + df * 16 + lg * 4) = (u32x2){pack_bf16x2(o[df][0] * inv, o[df][1] * inv), pack_bf16x2(o[df][2] * inv, o[df][3] * inv)};
+        store_o_row(p.out + ((long)b * p.Nq + qrow) * p.ldo + h * D, o, 1.0f / l_run, lg);   // contract: at least one live key per sample
     }
 }
 
@@ -248,140 +190,24 @@ __global__ __launch_bounds__(BI_D) void biattn_combine_kernel(const float* __res
 // ------------------------------------------------------------------------------------------------------------------ masked short attention
 constexpr int MS_NMAX = 256;
 
-struct MaskedArgs {
-    const bf16_t* q; const bf16_t* k; const bf16_t* v; const uint8_t* mask; bf16_t* o;
-    int H, N;
-    long q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, o_sb, o_sh, o_sn;
-    float scale;
+struct ByteMask {  // Mask policy of attn_masked_short_kernel: p.extra = uint8 [B*H, N, N], non-zero = the key is allowed
+    const uint8_t* mrow;   // allowed keys of this lane's query
+    int N;
+    static __device__ __forceinline__ void window(const ShortAttnArgs& p, int, int, int, int& ulo, int& uhi) { ulo = 0; uhi = p.N; }
+    __device__ __forceinline__ ByteMask(const ShortAttnArgs& p, int, int bh, int qc) : mrow((const uint8_t*)p.extra + ((long)bh * p.N + qc) * p.N), N(p.N) {}
+    __device__ __forceinline__ uint32_t frag(int key0) const {  // byte r: key key0 + r
+        uint32_t allow = 0u;
+        if ((N & 3) == 0) {  // a lane's 4 keys are then one aligned 4-byte read, all inside the row
+            if (key0 < N) allow = *reinterpret_cast<const uint32_t*>(mrow + key0);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (key0 + r < N) allow |= (mrow[key0 + r] ? 1u : 0u) << (8 * r);
+        }
+        return allow;
+    }
+    __device__ __forceinline__ bool on(uint32_t allow, int r) const { return (allow >> (8 * r)) & 0xffu; }
 };
-
-// One workgroup per (batch, head, 64 query rows), one 16-row query fragment per wave.  All keys of the head pass through ONE LDS buffer: first
-// the K rows (the whole logit row, <= 16 key fragments, then lives in registers and the softmax is one pass), then V^T.
-template <int D, int NKF>  // NKF: 16-key fragments a row may span (N <= 16 NKF), a multiple of 4 (V^T is permuted inside whole 64-key tiles)
-__global__ __launch_bounds__(256) void attn_masked_short_kernel(const MaskedArgs p) {
-    constexpr int NT = 256;
-    constexpr int NS = NKF * 16;    // staged keys (zeros past N)
-    constexpr int NC = D / 32;
-    constexpr int NDF = D / 16;
-    constexpr int DCH = D / 8;
-    constexpr int KROW = D + 8;
-    constexpr int VROW = NS + 8;
-    constexpr int BUF = (NS * KROW > D * VROW) ? NS * KROW : D * VROW;
-    static_assert((D == 32 || D == 64) && NKF % 4 == 0 && NKF * 16 <= MS_NMAX, "head_dim 32 or 64, whole 64-key tiles, at most 256 keys");
-
-    __shared__ __attribute__((aligned(16))) bf16_t sBuf[BUF];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l15 = lane & 15, lg = lane >> 4;
-    const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
-    const int N = p.N;
-    const int q0 = blockIdx.x * 64 + wave * 16;
-    const bool active = q0 < N;   // wave-uniform
-    const int qrow = q0 + l15, qc = min(qrow, N - 1);
-    const bf16_t* kp = p.k + (long)b * p.k_sb + (long)h * p.k_sh;
-    const bf16_t* vp = p.v + (long)b * p.v_sb + (long)h * p.v_sh;
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
-    const int nfrag = (N + 15) >> 4;
-
-    for (int id = tid; id < NS * DCH; id += NT) {
-        const int key = id / DCH, c = id - key * DCH;
-        const u32x4 t = key < N ? *reinterpret_cast<const u32x4*>(kp + (long)key * p.k_sn + c * 8) : zero4;
-        *reinterpret_cast<u32x4*>(sBuf + key * KROW + c * 8) = t;
-    }
-    __syncthreads();
-
-    f32x4 s[NKF];
-    float inv = 0.f;
-    if (active) {
-        bf16x8_t qf[NC];
-        const bf16_t* qr = p.q + (long)b * p.q_sb + (long)h * p.q_sh + (long)qc * p.q_sn;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) qf[c] = as_bf16x8(*reinterpret_cast<const u32x4*>(qr + c * 32 + lg * 8));
-        const uint8_t* mrow = p.mask + ((long)bh * N + qc) * N;   // allowed keys of this lane's query
-        const bool vec_mask = (N & 3) == 0;                       // a lane's 4 keys are then one aligned 4-byte read, all inside the row
-        const float c2 = p.scale * LOG2E;
-        float mx = NEG_BIG;
-#pragma unroll
-        for (int kf = 0; kf < NKF; ++kf) {
-            if (kf < nfrag) {
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    const bf16x8_t kfr = as_bf16x8(*reinterpret_cast<const u32x4*>(sBuf + (kf * 16 + l15) * KROW + c * 32 + lg * 8));
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr, qf[c], acc, 0, 0, 0);
-                }
-                const int key0 = kf * 16 + lg * 4;
-                uint32_t allow = 0u;
-                if (vec_mask) {
-                    if (key0 < N) allow = *reinterpret_cast<const uint32_t*>(mrow + key0);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (key0 + r < N) allow |= (mrow[key0 + r] ? 1u : 0u) << (8 * r);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float v = ((allow >> (8 * r)) & 0xffu) ? acc[r] * c2 : NEG_BIG;
-                    s[kf][r] = v;
-                    mx = fmaxf(mx, v);
-                }
-            } else {
-                s[kf] = (f32x4){NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG};
-            }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));   // contract: every row allows a key, so mx is a real logit
-        float rs = 0.f;
-#pragma unroll
-        for (int kf = 0; kf < NKF; ++kf)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = s[kf][r] > 0.5f * NEG_BIG ? __builtin_amdgcn_exp2f(s[kf][r] - mx) : 0.f;
-                s[kf][r] = e;
-                rs += e;
-            }
-        rs += __shfl_xor(rs, 16, 64);
-        rs += __shfl_xor(rs, 32, 64);
-        inv = 1.0f / rs;
-    }
-    __syncthreads();   // every wave has read the K rows
-
-    for (int id = tid; id < (NS / 2) * DCH; id += NT) {
-        const int pr = id / DCH, c = id - pr * DCH;
-        const int key = 2 * pr;
-        const u32x4 t0 = key < N ? *reinterpret_cast<const u32x4*>(vp + (long)key * p.v_sn + c * 8) : zero4;
-        const u32x4 t1 = key + 1 < N ? *reinterpret_cast<const u32x4*>(vp + (long)(key + 1) * p.v_sn + c * 8) : zero4;
-        store_vt_pair(sBuf, VROW, c, (key & ~63) + vt_pos(key & 63), t0, t1);
-    }
-    __syncthreads();   // the last barrier
-
-    if (!active) return;
-    f32x4 o[NDF];
-#pragma unroll
-    for (int df = 0; df < NDF; ++df) o[df] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < NKF / 2; ++j) {
-        if (2 * j < nfrag) {
-            u32x4 pw;
-            pw.x = pack_bf16x2(s[2 * j][0], s[2 * j][1]);
-            pw.y = pack_bf16x2(s[2 * j][2], s[2 * j][3]);
-            pw.z = pack_bf16x2(s[2 * j + 1][0], s[2 * j + 1][1]);
-            pw.w = pack_bf16x2(s[2 * j + 1][2], s[2 * j + 1][3]);
-            const bf16x8_t pb = as_bf16x8(pw);
-#pragma unroll
-            for (int df = 0; df < NDF; ++df) {
-                const bf16x8_t vf = as_bf16x8(*reinterpret_cast<const u32x4*>(sBuf + (df * 16 + l15) * VROW + (j >> 1) * 64 + lg * 16 + (j & 1) * 8));
-                o[df] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb, o[df], 0, 0, 0);
-            }
-        }
-    }
-    if (qrow < N) {
-        bf16_t* op = p.o + (long)b * p.o_sb + (long)h * p.o_sh + (long)qrow * p.o_sn;
-#pragma unroll
-        for (int df = 0; df < NDF; ++df)
-            *reinterpret_cast<u32x2*>(op + df * 16 + lg * 4) = (u32x2){pack_bf16x2(o[df][0] * inv, o[df][1] * inv), pack_bf16x2(o[df][2] * inv, o[df][3] * inv)};
-    }
-}
 
 // out = res + gamma * (u + bias): the residual of a sub-block whose branch is an fp32 product, rounded to bf16 once
 __global__ __launch_bounds__(256) void scale_residual_kernel(const float* __restrict__ u, long ldu, const float* __restrict__ bias, const float* __restrict__ gamma,
@@ -468,31 +294,18 @@ extern "C" int ae_biattn_bf16(const void* q, long ldq, const void* k, long ldk, 
 extern "C" int ae_attn_masked_short_bf16(const void* q, const void* k, const void* v, const void* mask, void* out, int B, int H, int N, int D, long q_sb, long q_sh,
                                          long q_sn, long k_sb, long k_sh, long k_sn, long v_sb, long v_sh, long v_sn, long o_sb, long o_sh, long o_sn, float scale,
                                          void* stream) {
-    AE_REQUIRE(q && k && v && mask && out, "ae_attn_masked_short_bf16: null pointer");
-    AE_REQUIRE(B > 0 && H > 0 && (long)B * H <= 65535, "ae_attn_masked_short_bf16: bad sizes B=%d H=%d (B*H at most 65535)", B, H);
-    AE_REQUIRE(N >= 1 && N <= MS_NMAX, "ae_attn_masked_short_bf16: sequence length %d outside [1, %d] (a whole row of keys lives in registers)", N, MS_NMAX);
-    AE_REQUIRE(D == 32 || D == 64, "ae_attn_masked_short_bf16: unsupported head_dim %d (supported: 32, 64)", D);
-    AE_REQUIRE((q_sb | q_sh | q_sn | k_sb | k_sh | k_sn | v_sb | v_sh | v_sn) % 8 == 0 && (o_sb | o_sh | o_sn) % 4 == 0,
-               "ae_attn_masked_short_bf16: strides must keep q/k/v rows 16-byte aligned and out rows 8-byte aligned");
-    AE_REQUIRE(q_sb >= 0 && q_sh >= 0 && q_sn >= 0 && k_sb >= 0 && k_sh >= 0 && k_sn >= 0 && v_sb >= 0 && v_sh >= 0 && v_sn >= 0 && o_sb >= 0 && o_sh >= 0 && o_sn >= D,
-               "ae_attn_masked_short_bf16: negative stride, or output rows that overlap");
-    AE_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)out & 7) == 0 && ((uintptr_t)mask & 3) == 0,
-               "ae_attn_masked_short_bf16: q/k/v must be 16-byte aligned, out 8-byte aligned, mask 4-byte aligned");
-    AE_REQUIRE(scale > 0.f, "ae_attn_masked_short_bf16: scale must be positive");
-    MaskedArgs a{};
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.mask = (const uint8_t*)mask; a.o = (bf16_t*)out;
-    a.H = H; a.N = N;
-    a.q_sb = q_sb; a.q_sh = q_sh; a.q_sn = q_sn; a.k_sb = k_sb; a.k_sh = k_sh; a.k_sn = k_sn;
-    a.v_sb = v_sb; a.v_sh = v_sh; a.v_sn = v_sn; a.o_sb = o_sb; a.o_sh = o_sh; a.o_sn = o_sn;
-    a.scale = scale;
+    static const ShortAttnRules rules{"ae_attn_masked_short_bf16", 65535, MS_NMAX, "a whole row of keys lives in registers", true, 4,
+                                      "q/k/v must be 16-byte aligned, out 8-byte aligned, mask 4-byte aligned"};
+    ShortAttnArgs a{};
+    if (const int e = short_attn_args(a, rules, q, k, v, mask, out, B, H, N, D, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, o_sb, o_sh, o_sn, scale)) return e;
     const dim3 grid((unsigned)((N + 63) / 64), (unsigned)(B * H)), block(256);
     const hipStream_t st = (hipStream_t)stream;
     if (D == 32) {
-        if (N <= 128) hipLaunchKernelGGL((attn_masked_short_kernel<32, 8>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((attn_masked_short_kernel<32, 16>), grid, block, 0, st, a);
+        if (N <= 128) hipLaunchKernelGGL((attn_masked_short_kernel<32, 8, ByteMask>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((attn_masked_short_kernel<32, 16, ByteMask>), grid, block, 0, st, a);
     } else {
-        if (N <= 128) hipLaunchKernelGGL((attn_masked_short_kernel<64, 8>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((attn_masked_short_kernel<64, 16>), grid, block, 0, st, a);
+        if (N <= 128) hipLaunchKernelGGL((attn_masked_short_kernel<64, 8, ByteMask>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((attn_masked_short_kernel<64, 16, ByteMask>), grid, block, 0, st, a);
     }
     return ae_check_launch("ae_attn_masked_short_bf16");
 }

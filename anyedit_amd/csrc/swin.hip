@@ -15,17 +15,13 @@
 // rolled or padded copy of the activation exists.  A token whose image coordinate lies outside the map is a PAD token: the reference pads norm1's
 // output with zeros and qkv has a bias, so its key and value are qkv_bias rounded to bf16 (what the GEMM stores for a zero row) and it takes part in
 // the softmax as a key; its output row does not exist and is never written.  K and V^T of the (window, head) are staged in LDS once (N = ws^2 <= 256
-// keys of head_dim 32: at most 37 KB), each wave owns 16-row query fragments qf = wave, wave + 4, ...  The MFMA operand placement is the one of
-// clip_text.hip: S^T = K Q^T with v_mfma_f32_16x16x32_bf16 (head_dim 32 is one K step), so a lane holds logits of ONE query row, the whole row
-// (<= 16 key fragments) lives in registers, the softmax is one fp32 pass and the exponentiated registers are already the B operand of
-// O^T = V^T P^T (probabilities rounded to bf16 only there).  Keys and query rows that exist only because N is padded up to whole fragments are
-// excluded outright: probability exactly 0, zero V, never stored.
-#include "common.hpp"
+// keys of head_dim 32: at most 37 KB), each wave owns 16-row query fragments qf = wave, wave + 4, ...  Operand placement, staging, the one-pass
+// softmax, PV and the store are the pieces of attn_short.hpp (head_dim 32 is one K step); particular to this kernel are the addressing table, the
+// pad keys read from the bias, and the relative-position bias and shift penalty added to the logits.
+#include "attn_short.hpp"
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float NEG_BIG = -1.0e30f;
 constexpr int SWIN_D = 32;
 
 struct SwinAttnArgs {
@@ -36,10 +32,6 @@ struct SwinAttnArgs {
     float scale;
 };
 
-__device__ __forceinline__ int vt_pos(int key) {  // inside one 64-key tile: key = 16 f + 4 g + r  ->  16 g + 4 f + r
-    return ((key >> 2) & 3) * 16 + (key >> 4) * 4 + (key & 3);
-}
-
 // BasicLayer.forward's three slices along one axis of the shifted frame: [0, L - ws), [L - ws, L - shift), [L - shift, L)
 __device__ __forceinline__ int shift_region(int p, int L, int ws, int shift) { return p < L - ws ? 0 : (p < L - shift ? 1 : 2); }
 
@@ -49,12 +41,25 @@ __device__ __forceinline__ u32x4 bias_chunk_bf16(const float* b) {  // 8 fp32 bi
     return (u32x4){pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(c[0], c[1]), pack_bf16x2(c[2], c[3])};
 }
 
+// loader of the window's staged keys: a real token from its image row, a pad token from the bias, no token as zeros
+struct WindowRows {
+    const bf16_t* base; long ld; const float* bias; const int* sRow;
+    __device__ __forceinline__ u32x4 operator()(int key, int c) const {
+        const int row = sRow[key];
+        return row >= 0 ? *reinterpret_cast<const u32x4*>(base + (long)row * ld + c * 8) : (row == -1 ? bias_chunk_bf16(bias + c * 8) : (u32x4){0u, 0u, 0u, 0u});
+    }
+};
+
+struct RealKey {  // the keys of the window among the nfrag fragments that were computed
+    int nfrag, N, lg;
+    __device__ __forceinline__ bool operator()(int kf, int r, float) const { return kf < nfrag && kf * 16 + lg * 4 + r < N; }
+};
+
 template <int NKF>  // 16-key fragments a row may span: N <= 16 NKF, NKF even (one PV MFMA contracts two)
 __global__ __launch_bounds__(256) void swin_window_attn_kernel(const SwinAttnArgs p) {
     constexpr int NT = 256;
     constexpr int D = SWIN_D;
     constexpr int NS = NKF * 16;                       // staged keys (zeros past N)
-    constexpr int DCH = D / 8;                         // 16-byte chunks per row
     constexpr int KROW = D + 8;                        // LDS row strides (elements), +16 B pad
     constexpr int VROW = (NS + 63) / 64 * 64 + 8;      // V^T is permuted inside whole 64-key tiles
     static_assert(NKF % 2 == 0 && NKF <= 16, "even number of key fragments, at most 256 keys");
@@ -91,34 +96,9 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const SwinAttnArg
     }
     __syncthreads();
 
-    // ---- stage K rows and V^T columns of all NS keys: a real token from its image row, a pad token from the bias, no token as zeros
-    const bf16_t* kbase = p.qkv + p.C + h * D;
-    const bf16_t* vbase = p.qkv + 2 * p.C + h * D;
-    const float* kbias = p.qkv_bias + p.C + h * D;
-    const float* vbias = p.qkv_bias + 2 * p.C + h * D;
-    for (int id = tid; id < NS * DCH; id += NT) {
-        const int key = id / DCH, c = id - key * DCH;
-        const int row = sRow[key];
-        const u32x4 t = row >= 0 ? *reinterpret_cast<const u32x4*>(kbase + (long)row * p.ldq + c * 8) : (row == -1 ? bias_chunk_bf16(kbias + c * 8) : zero4);
-        *reinterpret_cast<u32x4*>(sK + key * KROW + c * 8) = t;
-    }
-    for (int id = tid; id < (NS / 2) * DCH; id += NT) {
-        const int pr = id / DCH, c = id - pr * DCH;
-        const int key = 2 * pr;
-        const int r0 = sRow[key], r1 = sRow[key + 1];
-        const u32x4 t0 = r0 >= 0 ? *reinterpret_cast<const u32x4*>(vbase + (long)r0 * p.ldq + c * 8) : (r0 == -1 ? bias_chunk_bf16(vbias + c * 8) : zero4);
-        const u32x4 t1 = r1 >= 0 ? *reinterpret_cast<const u32x4*>(vbase + (long)r1 * p.ldq + c * 8) : (r1 == -1 ? bias_chunk_bf16(vbias + c * 8) : zero4);
-        const int pos = (key & ~63) + vt_pos(key & 63);  // even; key + 1 lands at pos + 1
-        const uint32_t a0[4] = {t0.x, t0.y, t0.z, t0.w};
-        const uint32_t a1[4] = {t1.x, t1.y, t1.z, t1.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const uint32_t lo = __builtin_amdgcn_perm(a1[e], a0[e], 0x05040100u);  // {a0.lo16, a1.lo16}: d = 8c + 2e
-            const uint32_t hi = __builtin_amdgcn_perm(a1[e], a0[e], 0x07060302u);  // {a0.hi16, a1.hi16}: d = 8c + 2e + 1
-            *reinterpret_cast<uint32_t*>(sVt + (c * 8 + 2 * e) * VROW + pos) = lo;
-            *reinterpret_cast<uint32_t*>(sVt + (c * 8 + 2 * e + 1) * VROW + pos) = hi;
-        }
-    }
+    // ---- stage K rows and V^T columns of all NS keys
+    stage_k_rows<D, NT>(sK, NS, tid, WindowRows{p.qkv + p.C + h * D, p.ldq, p.qkv_bias + p.C + h * D, sRow});
+    stage_vt<D, NT>(sVt, VROW, NS, tid, WindowRows{p.qkv + 2 * p.C + h * D, p.ldq, p.qkv_bias + 2 * p.C + h * D, sRow});
     __syncthreads();  // the last barrier: nothing below writes LDS
 
     const int nfrag = (N + 15) >> 4;  // key fragments that hold a real key
@@ -131,8 +111,8 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const SwinAttnArg
         const int orow = qrow < N ? sRow[qrow] : -2;  // image row this lane's query reads and writes; < 0: nothing to store
         const int qreg = sReg[qc];
 
-        // Q fragment (B operand of S^T = K Q^T): lane (q = l15, g) holds Q[q][8g .. +8]; rows that are never stored read zeros
-        const bf16x8_t qfr = as_bf16x8(orow >= 0 ? *reinterpret_cast<const u32x4*>(p.qkv + (long)orow * p.ldq + h * D + lg * 8) : zero4);
+        // Q fragment: rows that are never stored read zeros
+        const bf16x8_t qfr[1] = {as_bf16x8(orow >= 0 ? *reinterpret_cast<const u32x4*>(p.qkv + (long)orow * p.ldq + h * D + lg * 8) : zero4)};
 
         // ---- S^T = K Q^T: lane holds the logits of keys 16 kf + 4 g + r for query l15, fp32, in the exp2 domain
         f32x4 s[NKF];
@@ -141,8 +121,7 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const SwinAttnArg
         for (int kf = 0; kf < NKF; ++kf) {
             if (kf < nfrag) {
                 const int key0 = kf * 16 + lg * 4;
-                const bf16x8_t kfr = as_bf16x8(*reinterpret_cast<const u32x4*>(sK + (kf * 16 + l15) * KROW + lg * 8));
-                const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr, qfr, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                const f32x4 acc = logit_frag(sK, kf, qfr, l15, lg);
                 const float* bp = hbias + (long)qc * N + key0;
                 f32x4 bv = {0.f, 0.f, 0.f, 0.f};
                 if (vec_bias) {
@@ -165,51 +144,18 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const SwinAttnArg
                 s[kf] = (f32x4){NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG};
             }
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // key 0 exists for every row: mx is a real logit
-
-        // ---- one-pass softmax: the whole row is in registers
+        mx = query_max(mx);  // key 0 exists for every row: mx is a real logit
         float rs = 0.f;
 #pragma unroll
-        for (int kf = 0; kf < NKF; ++kf)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int key = kf * 16 + lg * 4 + r;
-                const float e = (kf < nfrag && key < N) ? __builtin_amdgcn_exp2f(s[kf][r] - mx) : 0.f;
-                s[kf][r] = e;
-                rs += e;
-            }
-        rs += __shfl_xor(rs, 16, 64);
-        rs += __shfl_xor(rs, 32, 64);
-        const float inv = 1.0f / rs;  // rs >= 1: the row maximum contributes exp2(0)
+        for (int kf = 0; kf < NKF; ++kf) s[kf] = exp_frag(s[kf], kf, mx, rs, RealKey{nfrag, N, lg});
+        const float inv = 1.0f / query_sum(rs);
 
-        // ---- O^T = V^T P^T: lane holds O^T[d = 16 df + 4 g + r][q = l15]; P as bf16, 32 keys (two fragments) per MFMA
         f32x4 o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-        for (int j = 0; j < NKF / 2; ++j) {
-            if (2 * j < nfrag) {
-                u32x4 pw;
-                pw.x = pack_bf16x2(s[2 * j][0], s[2 * j][1]);
-                pw.y = pack_bf16x2(s[2 * j][2], s[2 * j][3]);
-                pw.z = pack_bf16x2(s[2 * j + 1][0], s[2 * j + 1][1]);
-                pw.w = pack_bf16x2(s[2 * j + 1][2], s[2 * j + 1][3]);
-                const bf16x8_t pb = as_bf16x8(pw);
-#pragma unroll
-                for (int df = 0; df < 2; ++df) {
-                    const bf16x8_t vf = as_bf16x8(*reinterpret_cast<const u32x4*>(sVt + (df * 16 + l15) * VROW + (j >> 1) * 64 + lg * 16 + (j & 1) * 8));
-                    o[df] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb, o[df], 0, 0, 0);
-                }
-            }
-        }
-
-        // ---- normalise and store to the token's own image row: 4 consecutive d per lane -> 8-byte stores; pad and padding rows are never stored
-        if (orow >= 0) {
-#pragma unroll
-            for (int df = 0; df < 2; ++df) {
-                u32x2* dst = reinterpret_cast<u32x2*>(p.out + (long)orow * p.ldo + h * D + df * 16 + lg * 4);
-                *dst = (u32x2){pack_bf16x2(o[df][0] * inv, o[df][1] * inv), pack_bf16x2(o[df][2] * inv, o[df][3] * inv)};
-            }
-        }
+        for (int j = 0; j < NKF / 2; ++j)
+            if (2 * j < nfrag) pv_step(o, s[2 * j], s[2 * j + 1], sVt, VROW, pv_col(j, lg), l15);
+        // store to the token's own image row; pad and padding rows are never stored
+        if (orow >= 0) store_o_row(p.out + (long)orow * p.ldo + h * D, o, inv, lg);
     }
 }
 

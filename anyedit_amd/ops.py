@@ -671,19 +671,35 @@ def attention_bhnd(q, k, v, scale=None, key_mask=None):
 ACT_QUICK_GELU, ACT_GELU = 0, 1
 
 
+def _attention_short(name, fn, q, k, v, extra, B, H, N, D, scale, q_strides, k_strides, v_strides, out, max_n=None, dims=None):
+    """The part the three `attention_*_short` wrappers share.  extra: None, or (tensor, dtype, label, shape) of the mask / spans argument, which
+    the entry point `fn` takes behind v.  max_n / dims: the N and D ranges to refuse here (None: left to the entry point)."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _chk(t, BF16, f"{name}.{n}")
+    if max_n is not None and not 1 <= N <= max_n:
+        raise ValueError(f"{name}: sequence length {N}; {fn.__name__} takes between 1 and {max_n}")
+    if dims is not None and D not in dims:
+        raise ValueError(f"{name}: head_dim {D} is not built (supported: {', '.join(map(str, dims))})")
+    ptrs = [_p(q), _p(k), _p(v)]
+    if extra is not None:
+        t, dtype, label, shape = extra
+        _chk(t, dtype, f"{name}.{label}", 3)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{name}: {label} must be a contiguous {list(shape)} tensor, got {tuple(t.shape)}")
+        ptrs.append(_p(t))
+    if out is None:
+        out = torch.empty(B, N, H * D, dtype=BF16, device=q.device)
+    _chk(out, BF16, f"{name}.out")
+    if out.numel() != B * N * H * D or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous [{B}, {N}, {H * D}] buffer")
+    check(fn(*ptrs, _p(out), B, H, N, D, *q_strides, *k_strides, *v_strides, N * H * D, D, H * D, float(scale), _s()), fn.__name__)
+    return out
+
+
 def attention_causal_short(q, k, v, B, H, N, D, scale, q_strides, k_strides, v_strides, out=None):
     """Causal self-attention over at most 128 tokens (the CLIP text tower): q/k/v bf16 tensors addressed through (batch, head, row)
     element strides as in `attention`, out [B, N, H*D] bf16.  Row i attends keys [0, i].  N in [1, 128], D in {32, 64}."""
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        _chk(t, BF16, "attention_causal_short." + n)
-    if out is None:
-        out = torch.empty(B, N, H * D, dtype=BF16, device=q.device)
-    _chk(out, BF16, "attention_causal_short.out")
-    if out.numel() != B * N * H * D or not out.is_contiguous():
-        raise ValueError(f"attention_causal_short: out must be a contiguous [{B}, {N}, {H * D}] buffer")
-    check(lib.ae_attn_causal_short_bf16(_p(q), _p(k), _p(v), _p(out), B, H, N, D, *q_strides, *k_strides, *v_strides, N * H * D, D, H * D,
-                                        float(scale), _s()), "ae_attn_causal_short_bf16")
-    return out
+    return _attention_short("attention_causal_short", lib.ae_attn_causal_short_bf16, q, k, v, None, B, H, N, D, scale, q_strides, k_strides, v_strides, out)
 
 
 def clip_embed(ids, token_table, position_table, out=None):
@@ -1043,25 +1059,10 @@ def attention_masked_short(q, k, v, mask, B, H, N, D, scale, q_strides, k_stride
     """Self-attention over at most 256 tokens with a full boolean mask (GroundingDINO's text layers): q/k/v bf16 tensors addressed through
     (batch, head, row) element strides as in `attention_causal_short`; mask uint8 (or bool) [B*H, N, N] contiguous, slice b*H + h, True = the key
     is ALLOWED for that query row; out [B, N, H*D] bf16.  CONTRACT: every row allows at least one key.  N in [1, 256], D in {32, 64}."""
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        _chk(t, BF16, "attention_masked_short." + n)
-    if not 1 <= N <= MASKED_SHORT_MAX_N:
-        raise ValueError(f"attention_masked_short: sequence length {N}; ae_attn_masked_short_bf16 takes between 1 and {MASKED_SHORT_MAX_N}")
-    if D not in (32, 64):
-        raise ValueError(f"attention_masked_short: head_dim {D} is not built (supported: 32, 64)")
     if mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)
-    _chk(mask, torch.uint8, "attention_masked_short.mask", 3)
-    if tuple(mask.shape) != (B * H, N, N) or not mask.is_contiguous():
-        raise ValueError(f"attention_masked_short: mask must be a contiguous [{B * H}, {N}, {N}] tensor, got {tuple(mask.shape)}")
-    if out is None:
-        out = torch.empty(B, N, H * D, dtype=BF16, device=q.device)
-    _chk(out, BF16, "attention_masked_short.out")
-    if out.numel() != B * N * H * D or not out.is_contiguous():
-        raise ValueError(f"attention_masked_short: out must be a contiguous [{B}, {N}, {H * D}] buffer")
-    check(lib.ae_attn_masked_short_bf16(_p(q), _p(k), _p(v), _p(mask), _p(out), B, H, N, D, *q_strides, *k_strides, *v_strides, N * H * D, D, H * D,
-                                        float(scale), _s()), "ae_attn_masked_short_bf16")
-    return out
+    return _attention_short("attention_masked_short", lib.ae_attn_masked_short_bf16, q, k, v, (mask, torch.uint8, "mask", (B * H, N, N)), B, H, N, D, scale,
+                            q_strides, k_strides, v_strides, out, MASKED_SHORT_MAX_N, (32, 64))
 
 
 # --------------------------------------------------------------------------- GroundingDINO text side (csrc/gdino_text.hip)
@@ -1144,23 +1145,8 @@ def attention_span_short(q, k, v, spans, B, H, N, D, scale, q_strides, k_strides
     """Self-attention over at most 256 tokens under a block-diagonal mask (BERT under GroundingDINO's sub-sentence masks): q/k/v bf16 tensors
     addressed through (batch, head, row) element strides as in `attention_masked_short`; spans int32 [B, N, 2] contiguous, shared by all heads:
     query n attends keys [lo, hi); out [B, N, H*D] bf16.  CONTRACT: 0 <= lo < hi <= N.  N in [1, 256], D == 64."""
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        _chk(t, BF16, "attention_span_short." + n)
-    if not 1 <= N <= TEXT_SPANS_MAX_N:
-        raise ValueError(f"attention_span_short: sequence length {N}; ae_attn_span_short_bf16 takes between 1 and {TEXT_SPANS_MAX_N}")
-    if D != 64:
-        raise ValueError(f"attention_span_short: head_dim {D} is not built (supported: 64)")
-    _chk(spans, torch.int32, "attention_span_short.spans", 3)
-    if tuple(spans.shape) != (B, N, 2) or not spans.is_contiguous():
-        raise ValueError(f"attention_span_short: spans must be a contiguous [{B}, {N}, 2] tensor, got {tuple(spans.shape)}")
-    if out is None:
-        out = torch.empty(B, N, H * D, dtype=BF16, device=q.device)
-    _chk(out, BF16, "attention_span_short.out")
-    if out.numel() != B * N * H * D or not out.is_contiguous():
-        raise ValueError(f"attention_span_short: out must be a contiguous [{B}, {N}, {H * D}] buffer")
-    check(lib.ae_attn_span_short_bf16(_p(q), _p(k), _p(v), _p(spans), _p(out), B, H, N, D, *q_strides, *k_strides, *v_strides, N * H * D, D, H * D,
-                                      float(scale), _s()), "ae_attn_span_short_bf16")
-    return out
+    return _attention_short("attention_span_short", lib.ae_attn_span_short_bf16, q, k, v, (spans, torch.int32, "spans", (B, N, 2)), B, H, N, D, scale,
+                            q_strides, k_strides, v_strides, out, TEXT_SPANS_MAX_N, (64,))
 
 
 # --------------------------------------------------------------------------- GroundingDINO query selection / decoder (csrc/gdino_decoder.hip)

@@ -56,13 +56,17 @@ def _span_reference(qkv, spans, B, H, N):
     return ref, bnd, v.transpose(1, 2).reshape(B, N, C)
 
 
-def _span_launch(qkv_d, spans_d, B, H, N):
+def _span_launch(qkv_d, spans_d, B, H, N, dense_d=None):
+    """attention_span_short between sentinel guards; with `dense_d` (uint8 [B*H, N, N]) attention_masked_short on the same q, k, v instead."""
     from anyedit_amd import ops
     C = H * 64
     buf = torch.full((B * N * C + 2 * GUARD,), SENTINEL, dtype=BF, device=DEV)
     out = buf[GUARD:GUARD + B * N * C].view(B, N, C)
     st = (N * 3 * C, 64, 3 * C)
-    ops.attention_span_short(qkv_d, qkv_d[:, C:], qkv_d[:, 2 * C:], spans_d, B, H, N, 64, 64 ** -0.5, st, st, st, out=out)
+    if dense_d is None:
+        ops.attention_span_short(qkv_d, qkv_d[:, C:], qkv_d[:, 2 * C:], spans_d, B, H, N, 64, 64 ** -0.5, st, st, st, out=out)
+    else:
+        ops.attention_masked_short(qkv_d, qkv_d[:, C:], qkv_d[:, 2 * C:], dense_d, B, H, N, 64, 64 ** -0.5, st, st, st, out=out)
     torch.cuda.synchronize()
     assert bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[-GUARD:] == SENTINEL).all()), "a store outside the output"
     return out.clone()
@@ -99,6 +103,21 @@ def test_span_attention_vs_float64(N, B, H, kind):
         dirty = qkv.view(B, N, 3 * C).clone()
         dirty[:, cut:, C:] = (1.0e4 * torch.randn(B, N - cut, 2 * C, generator=gen)).to(BF)
         assert torch.equal(_span_launch(dirty.view(B * N, 3 * C).to(DEV), clipped, B, H, N), base), "a key outside every span reached the output"
+
+
+@pytest.mark.parametrize("N,kind", [(N, kind) for N in (17, 65, 129, 256) for kind in ("partition", "midtile") if kind != "midtile" or N >= 128])
+def test_span_and_byte_mask_attention_are_one_kernel_body(N, kind):
+    """Spans s and the dense mask spans_to_mask(s), expanded to [B*H, N, N], are two mask policies of ONE kernel body (csrc/attn_short.hpp): the
+    outputs are bit-identical.  A span window starts on a multiple of 64, so a lane owns the same keys under both policies; a masked key adds an
+    exact zero to the row sum and to O; 64-key tiles and fragment pairs line up.  (`midtile` needs two key tiles: N >= 128, as in _SPAN_CASES.)"""
+    B, H = 2, 3
+    gen = torch.Generator().manual_seed(7000 + 10 * N + len(kind))
+    qkv_d = torch.randn(B * N, 3 * H * 64, generator=gen).to(BF).to(DEV)
+    spans = _layout(kind, B, N, gen)
+    dense_d = R.spans_to_mask(spans)[:, None].expand(B, H, N, N).reshape(B * H, N, N).to(torch.uint8).contiguous().to(DEV)
+    by_span = _span_launch(qkv_d, spans.to(torch.int32).to(DEV), B, H, N)
+    by_mask = _span_launch(qkv_d, None, B, H, N, dense_d=dense_d)
+    assert torch.equal(by_span, by_mask), f"{int((by_span != by_mask).sum())} elements differ between the span and the byte-mask policy"
 
 
 def test_span_attention_refusals():
