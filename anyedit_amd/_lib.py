@@ -108,7 +108,7 @@ SIGNATURES = {
     "ae_nms_sorted_f32": [c_void_p, c_void_p, c_int, c_float, c_void_p],
     "ae_sam_preprocess_f32": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "ae_patchify_f32_bf16": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    "ae_mse_f32": [c_void_p, c_void_p, c_void_p, c_long, c_void_p],
+    "ae_mse_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
     "ae_lincomb4_f32": [c_void_p, c_void_p, c_float, c_void_p, c_float, c_void_p, c_float, c_void_p, c_float, c_long, c_void_p],
     "ae_dpm_adaptive_err_f32": [c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_long, c_void_p, c_void_p],
     "ae_task_gate": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],

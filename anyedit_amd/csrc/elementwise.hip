@@ -8,7 +8,7 @@
 //       and the masked-latent blend (ddim.py:154-157 / global_tool.py:183-184);
 //   A10 SAM window_partition / window_unpartition (image_encoder.py:243-289), decomposed rel-pos terms (:325-355),
 //       PatchEmbed im2col (:364-395);
-//   A11 eps-MSE reduction (train.py:696).
+//   A11 eps-MSE reduction (train.py:696), bit-reproducible (two launches, no float atomics).
 // The DDIM update is compiled with fp contraction OFF so that, given the same eps, it is bit-identical to the
 // reference's unfused fp32 torch expression sequence.
 #include "common.hpp"
@@ -543,9 +543,11 @@ __global__ void patchify_kernel(const float* x, bf16_t* y, int B, int Cin, int H
     }
 }
 
-// sum((a-b)^2) -> out[0] via one atomicAdd per block (caller zeroes out first; scaled by inv_n)
-__global__ void mse_kernel(const float* a, const float* b, float* out, long n, float inv_n) {
-    __shared__ float red[4];
+// mean((a-b)^2) in two launches, bit-reproducible: every block stores the sum of its grid-stride share (fixed order), one block adds the
+// partial sums in block order.  (One float atomicAdd per block into out[0] gave a last-bit difference from run to run: the order of arrival.)
+constexpr int MSE_MAX_BLOCKS = 1024;
+__global__ __launch_bounds__(NT) void mse_partial_kernel(const float* a, const float* b, float* partial, long n) {
+    __shared__ float red[NT / 64];
     float s = 0.f;
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
         const float d = a[i] - b[i];
@@ -554,7 +556,16 @@ __global__ void mse_kernel(const float* a, const float* b, float* out, long n, f
     s = wave_reduce_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1] + red[2] + red[3]) * inv_n);
+    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(NT) void mse_final_kernel(const float* partial, int nb, float* out, float inv_n) {
+    __shared__ float red[NT / 64];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < nb; i += NT) s += partial[i];
+    s = wave_reduce_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = ((red[0] + red[1]) + (red[2] + red[3])) * inv_n;
 }
 
 inline unsigned grid_for(long n, int per_thread = 1) {
@@ -837,10 +848,12 @@ extern "C" int ae_dpm_adaptive_err_f32(const float* x_lower, const float* x_high
     return ae_check_launch("ae_dpm_adaptive_err_f32");
 }
 
-extern "C" int ae_mse_f32(const float* a, const float* b, float* out, long n, void* stream) {
-    AE_REQUIRE(a && b && out && n > 0, "ae_mse_f32: bad arguments");
-    hipError_t e = hipMemsetAsync(out, 0, sizeof(float), (hipStream_t)stream);
-    if (e != hipSuccess) { ae_set_error("ae_mse_f32: memset failed: %s", hipGetErrorString(e)); return AE_ERR_LAUNCH; }
-    hipLaunchKernelGGL(mse_kernel, dim3(grid_for(n) > 1024 ? 1024 : grid_for(n)), dim3(NT), 0, (hipStream_t)stream, a, b, out, n, 1.0f / (float)n);
+extern "C" int ae_mse_f32(const float* a, const float* b, float* out, float* partial, long n, void* stream) {
+    AE_REQUIRE(a && b && out && partial && n > 0, "ae_mse_f32: bad arguments (partial: 1024 floats of scratch)");
+    const unsigned nb = grid_for(n) > (unsigned)MSE_MAX_BLOCKS ? (unsigned)MSE_MAX_BLOCKS : grid_for(n);
+    hipLaunchKernelGGL(mse_partial_kernel, dim3(nb), dim3(NT), 0, (hipStream_t)stream, a, b, partial, n);
+    const int rc = ae_check_launch("ae_mse_f32(partial sums)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, (const float*)partial, (int)nb, out, 1.0f / (float)n);
     return ae_check_launch("ae_mse_f32");
 }

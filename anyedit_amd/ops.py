@@ -81,6 +81,20 @@ def _chk(t, dtype, name, dims=None):
         raise ValueError(f"{name}: expected {dims} dims, got shape {tuple(t.shape)}")
 
 
+def _dense(t, dtype, name, dims=None):
+    """`t` as the kernels read it: a GPU tensor of `dtype` (TypeError otherwise), copied if its layout is not row-major contiguous"""
+    _chk(t, dtype, name, dims)
+    return t.contiguous()
+
+
+def _target(t, dtype, shape, name):
+    """a tensor a kernel writes in place: it must already be contiguous (a copy would not reach the caller)"""
+    _chk(t, dtype, name)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous {tuple(shape)} tensor, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t
+
+
 # --------------------------------------------------------------------------- weight packing (host side, once)
 def pack_linear(w):
     """nn.Linear / 1x1 conv weight -> bf16 [N, K] contiguous."""
@@ -1476,6 +1490,9 @@ def rows_to_nchw(x, B, H, W, out_dtype=torch.float32):
 def concat_channels(a, b):
     if _TAPE is not None and _TAPE.active:
         return _TAPE.concat_channels(a, b)
+    a, b = _dense(a, BF16, "concat_channels.a", 2), _dense(b, BF16, "concat_channels.b", 2)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"concat_channels: {a.shape[0]} rows against {b.shape[0]}")
     out = torch.empty(a.shape[0], a.shape[1] + b.shape[1], dtype=BF16, device=a.device)
     check(lib.ae_concat_channels_bf16(_p(a), a.shape[1], _p(b), b.shape[1], _p(out), a.shape[0], _s()), "ae_concat_channels_bf16")
     return out
@@ -1484,8 +1501,13 @@ def concat_channels(a, b):
 def split_channels(dy, ca, a=None, b=None, want_a=True, want_b=True):
     """Adjoint of `concat_channels`: (da, db) with da (+)= dy[:, :ca], db (+)= dy[:, ca:]; `a` / `b` are existing gradient
     buffers to add into (None: a fresh buffer is written).  One launch instead of two strided copies and two adds."""
+    dy = _dense(dy, BF16, "split_channels.dy", 2)
     rows, C = dy.shape
     cb = C - ca
+    if a is not None:
+        _target(a, BF16, (rows, ca), "split_channels.a")
+    if b is not None:
+        _target(b, BF16, (rows, cb), "split_channels.b")
     da = a if a is not None else (torch.empty(rows, ca, dtype=BF16, device=dy.device) if want_a else None)
     db = b if b is not None else (torch.empty(rows, cb, dtype=BF16, device=dy.device) if want_b else None)
     check(lib.ae_split_channels_bf16(_p(dy), ca, cb, _p(da), _p(db), rows, int(a is not None), int(b is not None), _s()), "ae_split_channels_bf16")
@@ -1511,6 +1533,10 @@ def ddim_step(x, eps, coeffs, branches, s0=1.0, s1=0.0, noise=None, temperature=
     n = x.numel()
     if eps.numel() != branches * n:
         raise ValueError(f"ddim_step: eps has {eps.numel()} elements, expected {branches}*{n}")
+    if noise is not None:
+        noise = _dense(noise, torch.float32, "ddim_step.noise")
+        if noise.numel() != n:
+            raise ValueError(f"ddim_step: noise has {noise.numel()} elements, expected {n}")
     x_prev = torch.empty_like(x)
     pred_x0 = torch.empty_like(x) if want_pred_x0 else None
     s1m, sat, sap, dirc, sig = coeffs
@@ -1562,7 +1588,7 @@ def plms_combine(e_t, old_eps):
 
 
 def plms_combine_first(e_t, e_t_next):
-    out = torch.empty_like(e_t)
+    out = torch.empty(e_t.shape, dtype=e_t.dtype, device=e_t.device)   # contiguous like the kernel's view of the inputs (empty_like keeps a dense permuted layout)
     check(lib.ae_plms_combine_f32(_p(_tmp(e_t.contiguous())), _p(_tmp(e_t_next.contiguous())), None, None, _p(out), e_t.numel(), 0, _s()),
           "ae_plms_combine_f32")
     return out
@@ -1583,7 +1609,7 @@ def mask_blend_shape(mask, B, C, H, W):
 
 def mask_blend(img, x0, noise, mask, sqrt_ac, sqrt_one_minus_ac, ip2p_order=False):
     B, C, H, W = img.shape
-    out = torch.empty_like(img)
+    out = torch.empty(img.shape, dtype=img.dtype, device=img.device)   # the kernel writes row-major (not empty_like: see plms_combine_first)
     m, Bk, Ck = mask_blend_shape(mask, B, C, H, W)
     check(lib.ae_mask_blend_f32(_p(_tmp(img.contiguous())), _p(_tmp(x0.contiguous())), _p(_tmp(noise.contiguous())), _p(_tmp(m.contiguous().float())),
                                 _p(out), Bk, Ck, H * W, sqrt_ac, sqrt_one_minus_ac, 1 if ip2p_order else 0, _s()), "ae_mask_blend_f32")
@@ -1592,7 +1618,7 @@ def mask_blend(img, x0, noise, mask, sqrt_ac, sqrt_one_minus_ac, ip2p_order=Fals
 
 def q_sample(x0, noise, sqrt_ac_t, sqrt_one_minus_ac_t):
     """per-sample fp32 coefficient vectors [B] (already gathered at t)."""
-    out = torch.empty_like(x0)
+    out = torch.empty(x0.shape, dtype=x0.dtype, device=x0.device)      # row-major (see plms_combine_first)
     B = x0.shape[0]
     check(lib.ae_q_sample_f32(_p(_tmp(x0.contiguous())), _p(_tmp(noise.contiguous())), _p(_tmp(sqrt_ac_t.contiguous())),
                               _p(_tmp(sqrt_one_minus_ac_t.contiguous())), _p(out), B, x0.numel() // B, _s()), "ae_q_sample_f32")
@@ -1608,6 +1634,7 @@ def silu_to_bf16(x):
 
 
 def add_bcast(x, p):
+    x, p = _dense(x, BF16, "add_bcast.x"), _dense(p, BF16, "add_bcast.p")
     out = torch.empty_like(x)
     check(lib.ae_add_bcast_bf16(_p(x), _p(p), _p(out), x.numel(), p.numel(), _s()), "ae_add_bcast_bf16")
     return out
@@ -1708,6 +1735,7 @@ def window_merge_layernorm(windows, shortcut, gamma, beta, eps, B, H, W, ws, out
 
 
 def sam_relpos_terms(q, q_strides, Rh, Rw, B, heads, qH, qW, D):
+    Rh, Rw = _dense(Rh, torch.float32, "sam_relpos_terms.Rh", 3), _dense(Rw, torch.float32, "sam_relpos_terms.Rw", 3)
     kH, kW = Rh.shape[1], Rw.shape[1]
     rel_h = torch.empty(B * heads, qH * qW, kH, dtype=torch.float32, device=q.device)
     rel_w = torch.empty(B * heads, qH * qW, kW, dtype=torch.float32, device=q.device)
@@ -1719,6 +1747,8 @@ def sam_relpos_terms(q, q_strides, Rh, Rw, B, heads, qH, qW, D):
 def softmax_rows(S, scale):
     """softmax(scale * S) over the last dim: fp32 [R, N] (row stride free) -> bf16 [R, N]."""
     _chk(S, torch.float32, "softmax_rows.S", 2)
+    if S.stride(1) != 1 and S.shape[1] > 1:
+        S = S.contiguous()
     out = torch.empty(S.shape, dtype=BF16, device=S.device)
     check(lib.ae_softmax_rows_f32_bf16(_p(S), S.stride(0), _p(out), out.stride(0), S.shape[0], S.shape[1], float(scale), _s()),
           "ae_softmax_rows_f32_bf16")
@@ -1940,9 +1970,9 @@ def dpm_adaptive_err(x_lower, x_higher, x_prev, atol, rtol):
 
 
 def mse(a, b):
-    out = torch.empty(1, dtype=torch.float32, device=a.device)
-    check(lib.ae_mse_f32(_p(_tmp(a.float().contiguous())), _p(_tmp(b.float().contiguous())), _p(out), a.numel(), _s()), "ae_mse_f32")
-    return out[0]
+    ws = torch.empty(1 + 1024, dtype=torch.float32, device=a.device)    # the result and the per-block partial sums
+    check(lib.ae_mse_f32(_p(_tmp(a.float().contiguous())), _p(_tmp(b.float().contiguous())), _p(ws), _p(ws[1:]), a.numel(), _s()), "ae_mse_f32")
+    return ws[0]
 
 
 def task_gate(task_emb, edit_code, Wg, bg):
@@ -1992,7 +2022,7 @@ def geglu(h):
 
 
 def geglu_bwd(h, dy):
-    dh = torch.empty_like(h)
+    dh = torch.empty(h.shape, dtype=h.dtype, device=h.device)          # row-major like the kernel's view of h (see plms_combine_first)
     check(lib.ae_geglu_bwd_bf16(_p(_tmp(h.contiguous())), _p(_tmp(dy.contiguous())), _p(dh), h.shape[0], h.shape[1] // 2, _s()), "ae_geglu_bwd_bf16")
     return dh
 
@@ -2049,6 +2079,9 @@ def sumpool2x2(x, B, H, W):
 
 
 def colsum(x):
+    _chk(x, BF16, "colsum.x", 2)
+    if x.stride(1) != 1 and x.shape[1] > 1:
+        x = x.contiguous()
     out = torch.empty(x.shape[1], dtype=torch.float32, device=x.device)
     check(lib.ae_colsum_bf16_f32(_p(x), _p(out), x.shape[0], x.shape[1], x.stride(0), _s()), "ae_colsum_bf16_f32")
     return out

@@ -301,8 +301,9 @@ int ae_sam_relpos_terms(const void* q, long q_sb, long q_sh, long q_sn, const fl
                         float* rel_w, int B, int heads, int qH, int qW, int kH, int kW, int D, void* stream);
 /* PatchEmbed im2col (image_encoder.py:364-395): [B,Cin,H,W] fp32 -> [B*(H/P)*(W/P), Cin*P*P] bf16.                            */
 int ae_patchify_f32_bf16(const float* x, void* y, int B, int Cin, int H, int W, int P, void* stream);
-/* mean((a-b)^2) -> out[0] (train.py:696, ddpm.py:367-380).                                                                    */
-int ae_mse_f32(const float* a, const float* b, float* out, long n, void* stream);
+/* mean((a-b)^2) -> out[0] (train.py:696, ddpm.py:367-380).  partial: 1024 floats of scratch for the per-block sums, which a second
+ * launch adds in block order (the same bits on every run).                                                                   */
+int ae_mse_f32(const float* a, const float* b, float* out, float* partial, long n, void* stream);
 /* AnySD task router (OUR spec, reference source absent — SURVEY.md §8a row A9): logits = task_emb[edit_code] @ Wg^T + bg,
  * softmax over E experts, top-1 index + probability per sample.                                                              */
 int ae_task_gate(const float* task_emb, const long* edit_code, const float* Wg, const float* bg, int B, int n_tasks, int Dt,

@@ -2,9 +2,10 @@
 guidance batching — against the outputs of the reference's own samplers (tests/golden/*.npz).
 
 The product samplers call elementwise HIP kernels for the per-step arithmetic (there is no CPU path in the product, by design).  Here — in
-tests/ only — those kernels are replaced by `_StandIns`: the formulas their headers in csrc/elementwise.hip state, written in torch, so that
+tests/ only — those kernels are replaced by `small_ref.SamplerStandIns`: the formulas their headers in csrc/elementwise.hip state, written in torch, so that
 everything AROUND the kernels (the part that is Python in the product as well) runs on a box without a GPU.  Whether the kernels compute
-those formulas is what the `-m gpu` twins of these tests check (tests/test_hip_unet.py::test_plms_sampler_golden, …_ddim_sampler_v_prediction_golden,
+those formulas is what tests/test_hip_small_kernels.py checks, kernel against stand-in bit for bit, and the `-m gpu` twins of these tests
+(tests/test_hip_unet.py::test_plms_sampler_golden, …_ddim_sampler_v_prediction_golden,
 …_ddim_hacked_sampler_golden, …_dpm_solver_sampler_golden, …_dpm_solver_general_variants_golden)."""
 import numpy as np
 import pytest
@@ -13,91 +14,7 @@ import torch
 from conftest import load_golden, T
 from dpm_cases import DPM_GENERAL_CASES
 from oracle import schedule_ref as S
-
-
-class _StandIns:
-    """torch statements of the sampler kernels' documented arithmetic (csrc/elementwise.hip:96-222, 418-470)."""
-
-    @staticmethod
-    def _guided(eps, n_like, branches, s0, s1=0.0):
-        parts = eps.reshape(branches, *n_like.shape)
-        if branches == 1:
-            return parts[0]
-        if branches == 2:                                                   # [uncond, cond]
-            return parts[0] + s0 * (parts[1] - parts[0])
-        et, ei, eu = parts                                                   # [text, image, uncond]
-        return eu + s0 * (et - ei) + s1 * (ei - eu)
-
-    @classmethod
-    def ddim_step(cls, x, eps, coeffs, branches, s0=1.0, s1=0.0, noise=None, temperature=1.0, want_pred_x0=True, want_e=False):
-        s1m, sat, sap, dirc, sig = (torch.tensor(c, dtype=torch.float32) for c in coeffs)
-        e = cls._guided(eps, x, branches, s0, s1)
-        px0 = (x - s1m * e) / sat
-        nz = sig * (noise if noise is not None else torch.zeros_like(x)) * temperature
-        x_prev = sap * px0 + dirc * e + nz
-        return (x_prev, px0, e) if want_e else (x_prev, px0)
-
-    @classmethod
-    def ddim_encode_step(cls, x, eps, cx, ce, branches=1, scale=1.0):
-        e = cls._guided(eps, x, branches, scale)
-        return torch.tensor(cx, dtype=torch.float32) * x + torch.tensor(ce, dtype=torch.float32) * e
-
-    @staticmethod
-    def plms_combine(e_t, old_eps):
-        o = list(old_eps[::-1][:3])
-        if len(o) == 1:
-            return (3.0 * e_t - o[0]) / 2.0
-        if len(o) == 2:
-            return ((23.0 * e_t - 16.0 * o[0]) + 5.0 * o[1]) / 12.0
-        return (((55.0 * e_t - 59.0 * o[0]) + 37.0 * o[1]) - 9.0 * o[2]) / 24.0
-
-    @staticmethod
-    def plms_combine_first(e_t, e_t_next):
-        return (e_t + e_t_next) / 2.0
-
-    @staticmethod
-    def mask_blend(img, x0, noise, mask, sqrt_ac, sqrt_one_minus_ac, ip2p_order=False):
-        q = torch.tensor(sqrt_ac, dtype=torch.float32) * x0 + torch.tensor(sqrt_one_minus_ac, dtype=torch.float32) * noise
-        m = mask.float()
-        return img * m + q * (1.0 - m) if ip2p_order else q * m + (1.0 - m) * img
-
-    @staticmethod
-    def q_sample(x0, noise, sqrt_ac_t, sqrt_one_minus_ac_t):
-        shape = (-1,) + (1,) * (x0.dim() - 1)
-        return sqrt_ac_t.reshape(shape) * x0 + sqrt_one_minus_ac_t.reshape(shape) * noise
-
-    @staticmethod
-    def dpm_multistep(x, model_out, branches, scale, sigma_s, alpha_s, predict_x0=True, v_param=False, m_prev=None, update=None, want_m=True):
-        f = lambda v: torch.tensor(v, dtype=torch.float32)
-        parts = model_out.reshape(branches, *x.shape)
-        conv = (lambda o: f(alpha_s) * o + f(sigma_s) * x) if v_param else (lambda o: o)
-        e = conv(parts[0])
-        if branches == 2:
-            e = e + f(scale) * (conv(parts[1]) - e)
-        m = (x - f(sigma_s) * e) / f(alpha_s) if predict_x0 else e
-        xn = None
-        if update is not None:
-            a, b, c, inv_r0 = update
-            xn = f(a) * x - f(b) * m
-            if m_prev is not None:
-                xn = xn - f(c) * (f(inv_r0) * (m - m_prev))
-        return (m if want_m else None), xn
-
-    @staticmethod
-    def lincomb(terms, out=None):
-        acc = None
-        for t, c in terms:
-            if t is None:
-                continue
-            term = torch.tensor(float(c), dtype=torch.float32) * t
-            acc = term if acc is None else acc + term
-        return acc
-
-    @staticmethod
-    def dpm_adaptive_err(x_lower, x_higher, x_prev, atol, rtol):
-        delta = torch.max(torch.full_like(x_lower, atol), rtol * torch.max(x_lower.abs(), x_prev.abs()))
-        d = ((x_higher - x_lower) / delta).reshape(x_lower.shape[0], -1)
-        return torch.sqrt((d * d).mean(1))
+from small_ref import SamplerStandIns as _StandIns
 
 
 @pytest.fixture()
