@@ -45,8 +45,10 @@ constexpr int FF_MAXH2 = 2560;
 #endif
 constexpr int FF_OOB = 0x40000000;                            // a per-lane offset beyond every descriptor: the piece reads zeros
 
-// The gate of one row fragment (four values of a lane: a_half * (g + |g| w(g)), the arithmetic of geglu_half_f / gelu_w_f in common.hpp — bit-identical gated
-// values to the row-panel GEGLU epilogue) as 62 single VALU operations; operation u of a stage works on chain r = u & 3, so dependent operations sit four apart.
+// The gate of one row fragment (four values of a lane: a_half * (g + |g| w(g)), the arithmetic of geglu_half_f / gelu_w_f in common.hpp, operation for operation
+// as in the row-panel GEGLU epilogue.  The gated values are NOT bit-identical to that kernel's on every input, as this comment used to say: measured by
+// tools/rowpanel_route_check.py, about one row in 400 holds hidden values that differ by an ulp, several at a time — the pattern of one LayerNorm
+// operand rounded to its other bf16 neighbour by the two separately compiled prologues; both kernels stay within the float64 bound) as 62 single VALU operations; operation u of a stage works on chain r = u & 3, so dependent operations sit four apart.
 // Gate operations [ff_op_lo(P), ff_op_lo(P + 1)) of a phase (186 = 3 fragments x 62) go behind its MFMA P (90).
 constexpr int ff_op_lo(int P) { return (P * 186 + 89) / 90; }
 template <int U>

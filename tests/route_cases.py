@@ -1,5 +1,6 @@
-"""Route cases and the route ledger of gemm_conv.hip / attention_fast.hip (CASES, LEDGER: tools/route_check.py) and of norm.hip (NORM_CASES,
-NORM_LEDGER: tools/norm_route_check.py), shared with tests/test_kernel_routes.py.
+"""Route cases and the route ledger of gemm_conv.hip / attention_fast.hip (CASES, LEDGER: tools/route_check.py), of norm.hip (NORM_CASES,
+NORM_LEDGER: tools/norm_route_check.py) and of gemm_rowpanel.hip / ff_fused.hip (ROWPANEL_CASES, ROWPANEL_LEDGER:
+tools/rowpanel_route_check.py), shared with tests/test_kernel_routes.py.
 
 CASES: one dict per GPU case (op + shape + options); tools/route_check.py builds the seeded operands, runs the op through `ops`, records the
 kernels it launched and checks the output element by element (see that script's docstring for the bound).
@@ -394,6 +395,110 @@ for _C, _L in _NARROW.items():
         NORM_LEDGER[f"layernorm_narrow_kernel<{_L}, {int(_g)}>"] = ("default", _ids("lnact", C=_C, gelu=_g))
 
 
+# --------------------------------------------------------------------------------------------------- gemm_rowpanel.hip / ff_fused.hip: cases
+# rp:    ops.gemm (lnm 0) / ops.ln_gemm (lnm 1: LayerNorm prologue), K = 320: M, N, epi ("none" / "geglu"); bias (default present), res, ldr (residual
+#        row stride = N + ldr), aslice (A = columns 320..639 of a [M, 960] buffer), cpad (the output is a column slice of a buffer cpad + 8 wider),
+#        cs (column statistics of the output)
+# rs:    ops.gemm(rowstats=): the producer of a LayerNorm fold alone (bias + residual)
+# chain: that producer at N = 320, then ops.gemm_ln (LayerNorm fold) on its stored rows and statistics: N, epi, res (the consumer's)
+# ff:    ops.ff_fused: M, H, res, strided (x, w1, the output and the residual each with a row stride of its own), proj (None, or which of b3 / r3 /
+#        cs the projection behind the block carries)
+# env:   "hook" = the child runs with AE_ROWPANEL_ANY_M=1 (one block is enough), "default" = no AE_* variable (one 192-row block per CU from 192 blocks
+#        on); tiled = the case sits below that threshold and must run gemm_kernel instead, within the same bound
+# M: 192 one block, 193 a block with one live row, 207 / 208 / 209 a fragment's edge, 239 / 240 / 241 a wave's row-group edge, 383 two blocks less a row.
+# N / 64 in {1, 2, 3, 4, 5, 15, 40}: 2 is the ring's lead, 3 the ring, 40 = RP_MAXN.
+def _rp(id, M, N, epi="none", lnm=0, **kw):
+    return dict(id=id, op="rp", M=M, N=N, epi=epi, lnm=lnm, env=kw.pop("env", "hook"), **kw)
+
+
+def _ff(id, M, H, **kw):
+    return dict(id=id, op="ff", M=M, H=H, env=kw.pop("env", "hook"), res=kw.pop("res", False), strided=kw.pop("strided", False), proj=kw.pop("proj", None), **kw)
+
+
+RP_THRESHOLD_M = 191 * 192 + 1       # 192 blocks: the smallest M the default plan gives to the row-panel / fused feed-forward kernels
+ROWPANEL_CASES = [
+    # ---- plain, EPI none
+    _rp("rp_n64_m192", 192, 64),
+    _rp("rp_n128_m193", 193, 128, res=True),
+    _rp("rp_n192_m207_nobias", 207, 192, bias=False, res=True, ldr=40),
+    _rp("rp_n256_m208", 208, 256),
+    _rp("rp_n320_m209_slices", 209, 320, aslice=True, cpad=24, res=True, ldr=8),
+    _rp("rp_n960_m239", 239, 960, res=True),
+    _rp("rp_n2560_m240", 240, 2560),
+    _rp("rp_n320_m241_cs", 241, 320, cs=True),
+    _rp("rp_n320_m383", 383, 320, res=True),
+    _rp("rp_n320_threshold", RP_THRESHOLD_M, 320, res=True, env="default"),
+    _rp("rp_n320_below_threshold", RP_THRESHOLD_M - 1, 320, res=True, env="default", tiled=True),
+    # ---- plain, GEGLU
+    _rp("rpg_n128_m193", 193, 128, "geglu"),
+    _rp("rpg_n192_m383_nobias", 383, 192, "geglu", bias=False),
+    _rp("rpg_n256_m241_slices", 241, 256, "geglu", aslice=True, cpad=16),
+    _rp("rpg_n320_m208", 208, 320, "geglu"),
+    _rp("rpg_n2560_m192", 192, 2560, "geglu"),
+    # ---- LayerNorm prologue, EPI none
+    _rp("rpl_n64_m192", 192, 64, lnm=1),
+    _rp("rpl_n128_m208_cs", 208, 128, lnm=1, cs=True),
+    _rp("rpl_n192_m239", 239, 192, lnm=1, res=True),
+    _rp("rpl_n320_m193_slices", 193, 320, lnm=1, aslice=True, cpad=8, res=True, ldr=16),
+    _rp("rpl_n960_m209", 209, 960, lnm=1),
+    _rp("rpl_n2560_m383_nobias", 383, 2560, lnm=1, bias=False),
+    # ---- LayerNorm prologue, GEGLU
+    _rp("rplg_n128_m207_cs", 207, 128, "geglu", lnm=1, cs=True),
+    _rp("rplg_n192_m384", 384, 192, "geglu", lnm=1),
+    _rp("rplg_n320_m241", 241, 320, "geglu", lnm=1),
+    _rp("rplg_n2560_m193", 193, 2560, "geglu", lnm=1),
+    # ---- row statistics (the tail branch alone, an even and an odd number of pairs)
+    dict(id="rs_n64_m193", op="rs", M=193, N=64, res=True, env="hook"),
+    dict(id="rs_n128_m192", op="rs", M=192, N=128, res=False, env="hook"),
+    dict(id="rs_n128_m209", op="rs", M=209, N=128, res=True, env="hook"),
+    dict(id="rs_n320_m240", op="rs", M=240, N=320, res=True, env="hook"),
+    # ---- producer (row statistics, N = 320) -> LayerNorm fold
+    dict(id="chain_n64_m193", op="chain", M=193, N=64, epi="none", res=False, env="hook"),
+    dict(id="chain_n128_m207", op="chain", M=207, N=128, epi="none", res=True, env="hook"),
+    dict(id="chain_n192_m384", op="chain", M=384, N=192, epi="none", res=False, env="hook"),
+    dict(id="chain_n960_m241", op="chain", M=241, N=960, epi="none", res=False, env="hook"),
+    dict(id="chain_n960_m192", op="chain", M=192, N=960, epi="none", res=True, env="hook"),
+    dict(id="chain_n128g_m209", op="chain", M=209, N=128, epi="geglu", res=False, env="hook"),
+    dict(id="chain_n2560g_m192", op="chain", M=192, N=2560, epi="geglu", res=False, env="hook"),
+    dict(id="chain_n2560g_m383", op="chain", M=383, N=2560, epi="geglu", res=False, env="hook"),
+    # ---- fused feed-forward
+    _ff("ff_h64_m192", 192, 64, res=True),
+    _ff("ff_h128_m193", 193, 128),
+    _ff("ff_h1280_m241_strided", 241, 1280, res=True, strided=True),
+    _ff("ff_h64_m383_strided", 383, 64, strided=True),
+    _ff("ff_h1280_m383", 383, 1280, res=True),
+    _ff("ff_h64_threshold", RP_THRESHOLD_M, 64, res=True, env="default"),
+    _ff("ff_h64_below_threshold", RP_THRESHOLD_M - 1, 64, res=True, env="default", tiled=True),
+    _ff("ffp_h64_m193_all", 193, 64, res=True, proj=dict(b3=True, r3=True, cs=True)),
+    _ff("ffp_h128_m241_bare", 241, 128, proj=dict(b3=False, r3=False, cs=False)),
+    _ff("ffp_h1280_m192_b3_cs", 192, 1280, res=True, proj=dict(b3=True, r3=False, cs=True)),
+    _ff("ffp_h64_m383_r3_strided", 383, 64, res=True, strided=True, proj=dict(b3=False, r3=True, cs=False)),
+]
+ROWPANEL_CASE_IDS = [c["id"] for c in ROWPANEL_CASES]
+
+
+def _rk(epi, lnm, rs=False):
+    return f"gemm_rowpanel_kernel<10, {epi}, {lnm}, {str(rs).lower()}>"
+
+
+def _rpids(**kw):
+    return [c["id"] for c in ROWPANEL_CASES if not c.get("tiled") and all(c.get(k) == v for k, v in kw.items())]
+
+
+# gemm_rowpanel_kernel<KS, EPI (0 none, 2 GEGLU), LNM (0 plain, 1 LayerNorm prologue, 2 LayerNorm fold), RS (row statistics)>; ff_fused_kernel<PROJ>
+ROWPANEL_LEDGER = {
+    _rk(0, 0): ("default", _rpids(op="rp", epi="none", lnm=0)),
+    _rk(2, 0): ("default", _rpids(op="rp", epi="geglu", lnm=0)),
+    _rk(0, 1): ("default", _rpids(op="rp", epi="none", lnm=1)),
+    _rk(2, 1): ("default", _rpids(op="rp", epi="geglu", lnm=1)),      # (every feed-forward case runs it too, for the stored hidden activation)
+    _rk(0, 2): ("default", _rpids(op="chain", epi="none")),
+    _rk(2, 2): ("default", _rpids(op="chain", epi="geglu")),
+    _rk(0, 0, True): ("default", _rpids(op="rs") + _rpids(op="chain")),
+    "ff_fused_kernel<false>": ("default", _rpids(op="ff")),
+    "ff_fused_kernel<true>": ("default", [c["id"] for c in ROWPANEL_CASES if c["op"] == "ff" and c["proj"]]),
+}
+
+
 def expected_kernels(case_id):
     """ledger keys whose `default` row lists this case"""
-    return sorted(k for led in (LEDGER, NORM_LEDGER) for k, (kind, v) in led.items() if kind == "default" and case_id in v)
+    return sorted(k for led in (LEDGER, NORM_LEDGER, ROWPANEL_LEDGER) for k, (kind, v) in led.items() if kind == "default" and case_id in v)

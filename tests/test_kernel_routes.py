@@ -1,6 +1,7 @@
-"""Route ledger of gemm_conv.hip / attention_fast.hip / norm.hip (tests/route_cases.py) and the GPU route cases behind it.
+"""Route ledger of gemm_conv.hip / attention_fast.hip / norm.hip / gemm_rowpanel.hip / ff_fused.hip (tests/route_cases.py) and the GPU route
+cases behind it.
 
-CPU: the set of kernel instantiations the default build compiles — hipcc's device-only LLVM IR of the three sources with the library's flags
+CPU: the set of kernel instantiations the default build compiles — hipcc's device-only LLVM IR of the five sources with the library's flags
 (at -O0: which kernels a translation unit emits does not depend on the optimisation level) — must equal the ledger's keys, in both
 directions, so an instantiation that is added or removed fails here until someone classifies it.
 
@@ -9,6 +10,9 @@ with AE_ROWPANEL_ANY_M=1, set by test_hip_ops.py): every case must reach its dec
 check, leave its guard areas untouched and repeat bit for bit; every `default` ledger row must be reached by each case it lists.  Every
 attention case also carries the log-sum-exp outputs through the same checks and reports their worst error / bound as `lse_ratio`.
 The cases of norm.hip run the same way in a child process of their own (tools/norm_route_check.py, test_norm_route_cases_on_gpu).
+The cases of gemm_rowpanel.hip / ff_fused.hip (tools/rowpanel_route_check.py, test_rowpanel_route_cases_on_gpu) take two children: the
+small ones reach the kernels through the library's test hook, AE_ROWPANEL_ANY_M=1 in that child's environment only; the plan threshold
+(192 blocks of 192 rows run the kernels, 191 run the tiled gemm_kernel) is crossed from both sides with every AE_* variable removed.
 """
 import json
 import os
@@ -25,10 +29,12 @@ import route_cases as RC  # noqa: E402
 
 NORM_FAMILIES = ("gn_slab_kernel", "gn_apply_kernel", "gnb_slab_kernel", "layernorm_rows_kernel", "layernorm_kernel", "layernorm_window_kernel",
                  "layernorm_narrow_kernel", "layernorm_bwd_kernel")
-FAMILY_RE = re.compile(r"^void (?:\(anonymous namespace\)::)?(gemm_kernel|attn_fast_kernel|attn_pipe_kernel|" + "|".join(NORM_FAMILIES) + r")<([^<>]*)>\(")
+ROWPANEL_FAMILIES = ("gemm_rowpanel_kernel", "ff_fused_kernel")
+FAMILY_RE = re.compile(r"^void (?:\(anonymous namespace\)::)?(gemm_kernel|attn_fast_kernel|attn_pipe_kernel|" + "|".join(NORM_FAMILIES + ROWPANEL_FAMILIES) + r")<([^<>]*)>\(")
 NORM_PLAIN = ("gn_stats_kernel", "gn_finalize_kernel", "gn_finalize_cs_kernel", "gnb_partial_kernel", "gnb_finalize_kernel", "gnb_apply_kernel",
               "layernorm_param_grad_kernel")
 PLAIN = ("splitk_reduce_kernel", "colstats_kernel") + NORM_PLAIN
+ROWPANEL_CHILD_TIMEOUT = 120    # seconds for each child of tools/rowpanel_route_check.py; measured on the MI355X: 5.1 s (hook, 45 cases) and 8.8 s (default, 4 cases at M = 36673)
 NORM_CHILD_TIMEOUT = 180    # seconds for tools/norm_route_check.py; measured on the MI355X: 12 s for the whole child (8.8 s of cases and sweep)
 
 
@@ -49,7 +55,7 @@ def compiled_instantiations(tmpdir):
     from anyedit_amd import build as B
     hipcc = B._hipcc()
     keys = []
-    for src in ("gemm_conv.hip", "attention_fast.hip", "norm.hip"):
+    for src in ("gemm_conv.hip", "attention_fast.hip", "norm.hip", "gemm_rowpanel.hip", "ff_fused.hip"):
         flags = [("-O0" if f == "-O3" else f) for f in B.FLAGS if f != "-fPIC"] + B.EXTRA.get(src, [])
         out = os.path.join(str(tmpdir), src.replace(".hip", ".ll"))
         subprocess.run([hipcc] + flags + ["--cuda-device-only", "-emit-llvm", "-S", os.path.join(B.CSRC, src), "-o", out], check=True,
@@ -100,9 +106,9 @@ def test_norm_ledger_rows_are_well_formed():
 def test_ledger_equals_the_compiled_instantiations(tmp_path):
     keys = compiled_instantiations(tmp_path)
     assert len(keys) == len(set(keys)), "a kernel key appears twice"
-    ledger = set(RC.LEDGER) | set(RC.NORM_LEDGER)
+    ledger = set(RC.LEDGER) | set(RC.NORM_LEDGER) | set(RC.ROWPANEL_LEDGER)
     # (equality with the ledger's own count per family: a regular expression that silently finds nothing cannot pass)
-    for family in ("gemm_kernel<", "attn_") + tuple(f + "<" for f in NORM_FAMILIES) + NORM_PLAIN:
+    for family in ("gemm_kernel<", "attn_") + tuple(f + "<" for f in NORM_FAMILIES + ROWPANEL_FAMILIES) + NORM_PLAIN:
         assert sum(k.startswith(family) for k in keys) == sum(k.startswith(family) for k in ledger) > 0, (family, keys)
     compiled = set(keys)
     assert not compiled - ledger, f"instantiations without a ledger row (classify them in tests/route_cases.py): {sorted(compiled - ledger)}"
@@ -158,3 +164,40 @@ def test_norm_route_cases_on_gpu():
         f"{i} {r['ratio']:.3f}" + (f" {r['stat_ratio']:.3f}" if r["stat_ratio"] is not None else "") for i, r in results.items()))
     print("conditioning sweep, worst |rstd^/rstd - 1| per route and |mean|/sigma: " + json.dumps(summary["conditioning"]))
     assert p.returncode == 0, p.stderr[-4000:]
+
+
+def _rowpanel_child(env_name):
+    env = {k: v for k, v in os.environ.items() if not k.startswith("AE_")}
+    if env_name == "hook":
+        env["AE_ROWPANEL_ANY_M"] = "1"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "rowpanel_route_check.py"), "--env", env_name], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=ROWPANEL_CHILD_TIMEOUT)
+    print(p.stdout)
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("ROWPANEL_ROUTE_SUMMARY ")]
+    assert lines, f"rowpanel_route_check.py --env {env_name} ended without a summary (exit {p.returncode}):\n{p.stdout[-4000:]}\n{p.stderr[-4000:]}"
+    summary = json.loads(lines[-1][len("ROWPANEL_ROUTE_SUMMARY "):])
+    assert summary["aborted"] is None, f"GPU work stopped at {summary['aborted']}"
+    assert p.returncode in (0, 1), p.stderr[-4000:]
+    return summary["results"]
+
+
+@pytest.mark.gpu
+def test_rowpanel_route_cases_on_gpu():
+    """gemm_rowpanel.hip / ff_fused.hip: every case reaches its ledger rows (the two cases below the plan threshold: the tiled gemm_kernel), passes
+    the element-wise float64 checks of tests/rowpanel_ref.py on every row, leaves its guards untouched and repeats bit for bit; prints the worst
+    error / bound per case and per instantiation."""
+    results = {r["id"]: r for env_name in ("hook", "default") for r in _rowpanel_child(env_name)}
+    assert set(results) == set(RC.ROWPANEL_CASE_IDS), sorted(set(RC.ROWPANEL_CASE_IDS) ^ set(results))
+    failed = {i: r["error"] for i, r in results.items() if not r["ok"]}
+    assert not failed, failed
+    unreached = [(k, c) for k, (kind, cases) in RC.ROWPANEL_LEDGER.items() for c in cases if k not in results[c]["keys"]]
+    assert not unreached, unreached
+    for c in RC.ROWPANEL_CASES:
+        if c.get("tiled"):
+            keys = results[c["id"]]["keys"]
+            assert any(k.startswith("gemm_kernel<") for k in keys) and not any(k.startswith(ROWPANEL_FAMILIES) for k in keys), (c["id"], keys)
+    assert all(r["guards"] == "intact" and isinstance(r["ratio"], float) and r["ratio"] <= 1.0 and all(v <= 1.0 for v in r["parts"].values())
+               for r in results.values())
+    print("worst error / bound per case: " + ", ".join(f"{i} {r['ratio']:.3f}" for i, r in results.items()))
+    print("worst error / bound per instantiation: " + ", ".join(
+        f"{k} {max(results[c]['ratio'] for c in cases):.3f}" for k, (kind, cases) in RC.ROWPANEL_LEDGER.items()))

@@ -169,7 +169,9 @@ def stats_check(got, y, slab_rows, what, per_row=False, sample_rows=0):
 
 
 # --------------------------------------------------------------------------------------------------- kernel names
-def route_keys(names):
+def route_keys(names, families=None):
+    """kernel names of a profiler capture -> (demangled names, ledger keys); families: the regular expression of another file's kernel templates"""
+    families = families or FAMILIES
     mangled = [n for n in names if n.startswith("_Z")]
     if mangled:
         dm = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True).stdout.split("\n")
@@ -177,7 +179,7 @@ def route_keys(names):
         names = [table.get(n, n) for n in names]
     keys = []
     for n in names:
-        m = FAMILIES.search(n)
+        m = families.search(n)
         if m:
             keys.append(f"{m.group(1)}<{', '.join(x.strip() for x in m.group(2).split(','))}>")
         elif "splitk_reduce_kernel" in n:
