@@ -22,6 +22,7 @@
 //   * XCD-aware bijective tile remap so tiles sharing an operand panel run on the same XCD's L2.
 #include "common.hpp"
 #include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 
 namespace {
@@ -1470,13 +1471,8 @@ Plan make_plan(int M, int N, int K, bool can_split) {
 }
 
 // Launch one instantiation; kernels that need more than 64 KiB of dynamic LDS get the opt-in attribute once.
-// Plan query (ae_gemm_ln_plan): launch() runs its whole selection with g_plan_query set and launches nothing; the sites that hold a row-statistics /
-// LayerNorm-fold instantiation report through `xe_done` in launch().  One selection code path for the launch and for the question "would it be covered".
-thread_local int g_plan_query = 0;
-
 template <typename Kern>
 int launch_kernel(Kern kern, unsigned grid, int threads, size_t lds, hipStream_t stream, const GemmArgs& a, const char* what) {
-    if (g_plan_query) return 0;
     if (lds > 64 * 1024) {
         static const void* done[32];
         static int ndone = 0;
@@ -1495,8 +1491,49 @@ int launch_kernel(Kern kern, unsigned grid, int threads, size_t lds, hipStream_t
     return ae_check_launch(what);
 }
 
+// What a launch selects (the ae_*_plan queries, AE_PLAN_INTS ints in this order): the template arguments of the gemm_kernel instantiation, its launch
+// geometry, and the launches that follow it.  launch() / launch_sub2() given a report run their whole selection, fill it and launch nothing — no HIP
+// call is made — so the launch and the question "what would run" are one code path.
+struct PlanReport {
+    int BM, BN, AMODE, WAVES_M, WAVES_N, GLDS, WAVES_K, STAGES, CS, LAB, WA, XE;
+    int grid, threads, lds, splitk;
+    int reduce, colstats;   // splitk_reduce_kernel / the stand-alone colstats_kernel follows
+    int rowpanel;           // dense LayerNorm-fold queries: the row-panel kernel's fold forms take the launch instead (nothing above is filled)
+};
+#define AE_PLAN_INTS 19   // as include/anyedit_hip.h states it
+static_assert(sizeof(PlanReport) == AE_PLAN_INTS * sizeof(int), "PlanReport is the int array of anyedit_hip.h");
+
+// well-aligned stand-ins for the operands of a plan query: under a report no address is dereferenced and nothing is launched
+void* const kQueryPtr = reinterpret_cast<void*>(uintptr_t(256));
+float* const kQueryF32 = reinterpret_cast<float*>(uintptr_t(256));
+int plan_out(int rc, const PlanReport& r, int* plan) {
+    if (!rc) memcpy(plan, &r, sizeof r);
+    return rc;
+}
+
+struct LaunchCtx { const GemmArgs& a; hipStream_t stream; const char* what; PlanReport* report; };
+
+// launch one gemm_kernel instantiation, or describe it from its own template arguments
+template <int BM, int BN, int AMODE, int WAVES_M = 2, int WAVES_N = 2, bool GLDS = false, int WAVES_K = 1, int STAGES = 2, bool CS = false, int LAB = 0, int WA = 0, int XE = 0>
+int run_tile(const LaunchCtx& c, long grid, size_t lds) {
+    constexpr int threads = 64 * WAVES_M * WAVES_N * WAVES_K;
+    if (c.report) {
+        *c.report = PlanReport{BM, BN, AMODE, WAVES_M, WAVES_N, GLDS, WAVES_K, STAGES, CS, LAB, WA, XE, (int)grid, threads, (int)lds, c.a.splitk, 0, 0, 0};
+        return 0;
+    }
+    return launch_kernel(gemm_kernel<BM, BN, AMODE, WAVES_M, WAVES_N, GLDS, WAVES_K, STAGES, CS, LAB, WA, XE>, (unsigned)grid, threads, lds, c.stream, c.a, c.what);
+}
+
+// the plain two-stage loop of a tile, LDS-DMA or register-staged loader
+template <int BM, int BN, int AMODE, int WAVES_M, int WAVES_N>
+int run_plain(const LaunchCtx& c, bool glds, long grid) {
+    const size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(bf16_t);
+    return glds ? run_tile<BM, BN, AMODE, WAVES_M, WAVES_N, true>(c, grid, lds) : run_tile<BM, BN, AMODE, WAVES_M, WAVES_N, false>(c, grid, lds);
+}
+
+// split_tile: make_plan's tile of a split plan (read only where a.splitk > 1)
 template <int AMODE>
-int launch(const GemmArgs& a_in, hipStream_t stream) {
+int launch(const GemmArgs& a_in, hipStream_t stream, PlanReport* report = nullptr, int split_tile = 0) {
     GemmArgs a = a_in;
     // each XCD's L2 sees a contiguous run of tile ids: put the tiles that share the LARGER operand panel next to each other.
     // Weights dominate at the 16x16 / 8x8 latent levels (M = 3072 / 768 rows against N x 9 Cin weights); the gather's 9x
@@ -1517,6 +1554,7 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
     const int kt_block = ((a.K + BK - 1) / BK + a.splitk - 1) / a.splitk;
     const bool conv = AMODE == A_CONV3;
     const char* what = conv ? "ae_conv3x3_bf16" : "ae_gemm_bf16";
+    const LaunchCtx lc{a, stream, what, report};
     // LDS-DMA loaders need whole-tile decisions: no K tail, no mixed-source tile, no upsample gather / padded channels
     static const int glds_env = getenv("AE_GEMM_GLDS") ? atoi(getenv("AE_GEMM_GLDS")) : 1;  // tuning knob (A/B on hardware)
     const bool glds = glds_env && (conv ? (a.Cin == a.CinPad) : (a.K % BK == 0 && (!a.A2 || a.Ksplit % BK == 0)));
@@ -1568,12 +1606,12 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
                          192 / a.Wd <= a.H + 1 &&   // the slab's image row is y0 + jr with ONE wrap into the next sample (a short-wide map would need a true modulo)
                          (a.splitk <= 1 || kt_block % 9 == 0);
     const size_t lds_slab = (size_t)2 * ((192 + 192 / 16 + 1 + 7) / 8) * 1024 + (size_t)2 * 320 * BK * sizeof(bf16_t);
-    if (conv && a.splitk > 1 && glds && make_plan(a.M, a.N, a.K, true).tile == 4) {  // split-K under the 192x320 tile (make_plan)
+    if (conv && a.splitk > 1 && glds && split_tile == 4) {  // split-K under the 192x320 tile (make_plan)
         const long t = (long)(a.M / 192) * (a.N / 320) * a.splitk;
         if constexpr (AMODE == A_CONV3) {
-            if (slab_ok) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 4>, (unsigned)t, 512, lds_slab, stream, a, what);
-            else if (!a.ups) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what);
-            else rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
+            if (slab_ok) rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 4>(lc, t, lds_slab);
+            else if (!a.ups) rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 3>(lc, t, lds_aa(192, 320));
+            else rc = run_tile<192, 320, A_CONV3, 2, 4, true>(lc, t, lds_of(192, 320, 2));
         }
         done = true;
     }
@@ -1593,16 +1631,16 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
                              (double)t128x / (double)(((t128x + 511) / 512) * 512) <= 0.72;
         if (fill >= 0.85 || xe_tail) {
             if constexpr (AMODE == A_DENSE) {
-                if (xe_tail || (a.epi == EPI_GEGLU && a.xe == 2)) { rc = launch_kernel(gemm_kernel<192, 320, A_DENSE, 4, 2, true, 1, 2, false, 0, 3, 2>, (unsigned)t, 512, lds_aa(192, 320) + 2 * 320 * sizeof(float), stream, a, what); xe_done = true; }
-                else if (a.epi == EPI_GEGLU) rc = launch_kernel(gemm_kernel<192, 320, A_DENSE, 4, 2, true, 1, 2, false, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what);
-                else rc = launch_kernel(gemm_kernel<192, 320, A_DENSE, 2, 4, true, 1, 2, false, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what);
+                if (xe_tail || (a.epi == EPI_GEGLU && a.xe == 2)) { rc = run_tile<192, 320, A_DENSE, 4, 2, true, 1, 2, false, 0, 3, 2>(lc, t, lds_aa(192, 320) + 2 * 320 * sizeof(float)); xe_done = true; }
+                else if (a.epi == EPI_GEGLU) rc = run_tile<192, 320, A_DENSE, 4, 2, true, 1, 2, false, 0, 3>(lc, t, lds_aa(192, 320));
+                else rc = run_tile<192, 320, A_DENSE, 2, 4, true, 1, 2, false, 0, 3>(lc, t, lds_aa(192, 320));
             } else {
 #ifdef AE_GEMM_ABLATE
-                if (lab_abl == 1) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 1>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
-                else if (lab_abl == 2) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 2>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
-                else if (lab_abl == 3) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 3>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
-                else if (lab_abl == 4) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 4>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
-                else if (lab_abl == 20) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, false>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);  // register-staged loader
+                if (lab_abl == 1) rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 1>(lc, t, lds_of(192, 320, 2));
+                else if (lab_abl == 2) rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 2>(lc, t, lds_of(192, 320, 2));
+                else if (lab_abl == 3) rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 3>(lc, t, lds_of(192, 320, 2));
+                else if (lab_abl == 4) rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 4>(lc, t, lds_of(192, 320, 2));
+                else if (lab_abl == 20) rc = run_tile<192, 320, A_CONV3, 2, 4, false>(lc, t, lds_of(192, 320, 2));  // register-staged loader
                 else
 #endif
                 if (!a.ups) {   // (the nearest-x2 gather: its per-piece address arithmetic measured 283 vs 273 us under the first form of the ping-pong loop; a second attempt with
@@ -1610,15 +1648,15 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
                                 //  tables in scratch memory, profiles/r04_v23_ups_pp.txt).  Two launches per evaluation; they stay on the round-3 loop.)
                     // the slab form of the loop (WA = 4) where its preconditions hold — chunk-major K, stride 1, K range starting at tap 0
                     // (whole image rows per tile, 16-row fragments inside one image row, at most 200 slab rows)
-                    if (slab_ok && cs_epi_ok) { rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, true, 0, 4>, (unsigned)t, 512, lds_slab, stream, a, what); cs_done = true; }
-                    else if (slab_ok) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 4>, (unsigned)t, 512, lds_slab, stream, a, what);
-                    else if (cs_epi_ok) { rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, true, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what); cs_done = true; }
-                    else rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 3>, (unsigned)t, 512, lds_aa(192, 320), stream, a, what);
+                    if (slab_ok && cs_epi_ok) { rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, true, 0, 4>(lc, t, lds_slab); cs_done = true; }
+                    else if (slab_ok) rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 4>(lc, t, lds_slab);
+                    else if (cs_epi_ok) { rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, true, 0, 3>(lc, t, lds_aa(192, 320)); cs_done = true; }
+                    else rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 3>(lc, t, lds_aa(192, 320));
                 } else if (cs_epi_ok) {
-                    rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, true>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
+                    rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, true>(lc, t, lds_of(192, 320, 2));
                     cs_done = true;
                 }
-                else rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true>, (unsigned)t, 512, lds_of(192, 320, 2), stream, a, what);
+                else rc = run_tile<192, 320, A_CONV3, 2, 4, true>(lc, t, lds_of(192, 320, 2));
             }
             done = true;
         }
@@ -1642,15 +1680,15 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
             const long t128 = (long)((a.M + 127) / 128) * (a.N / 128);
             const long t192 = (long)((a.M + 191) / 192) * (a.N / 128);
             if (t128 >= 128 && t128 <= 256) {
-                if (a.xe == 1) rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 3, false, 0, 0, 1>, (unsigned)t128, 512, lds_of(128, 128, 3), stream, a, what);
-                else if (a.xe) rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 3, false, 0, 0, 2>, (unsigned)t128, 512, lds_of(128, 128, 3), stream, a, what);
-                else rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 3>, (unsigned)t128, 512, lds_of(128, 128, 3), stream, a, what);
+                if (a.xe == 1) rc = run_tile<128, 128, A_DENSE, 4, 2, true, 1, 3, false, 0, 0, 1>(lc, t128, lds_of(128, 128, 3));
+                else if (a.xe) rc = run_tile<128, 128, A_DENSE, 4, 2, true, 1, 3, false, 0, 0, 2>(lc, t128, lds_of(128, 128, 3));
+                else rc = run_tile<128, 128, A_DENSE, 4, 2, true, 1, 3>(lc, t128, lds_of(128, 128, 3));
                 xe_done = a.xe != 0;
                 done = true;
             } else if (t128 > 256 && t192 >= 128 && t192 <= 256 && a.K >= 2560) {
                 // a taller tile that brings the grid down to one block per CU (SAM: M = 4096 x N = 1280 x K = 5120, 320 -> 220 blocks:
                 // 89 -> 80 us; at K = 1280 it is neutral, and a 256x128 tile for M = 4900 loses: 32.5 -> 38 us)
-                rc = launch_kernel(gemm_kernel<192, 128, A_DENSE, 4, 2, true, 1, 3>, (unsigned)t192, 512, lds_of(192, 128, 3), stream, a, what);
+                rc = run_tile<192, 128, A_DENSE, 4, 2, true, 1, 3>(lc, t192, lds_of(192, 128, 3));
                 done = true;
             }
         }
@@ -1658,57 +1696,55 @@ int launch(const GemmArgs& a_in, hipStream_t stream) {
     if (!done) {
         const int BM = cand[pick][0], BN = cand[pick][1];
         const unsigned grid = (unsigned)((long)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * a.splitk);
-#define AE_LAUNCH(BM_, BN_, WM_, WN_, THREADS)                                                                                            \
-    do {                                                                                                                                  \
-        if (glds) rc = launch_kernel(gemm_kernel<BM_, BN_, AMODE, WM_, WN_, true>, grid, THREADS, lds_of(BM_, BN_, 2), stream, a, what);   \
-        else rc = launch_kernel(gemm_kernel<BM_, BN_, AMODE, WM_, WN_, false>, grid, THREADS, lds_of(BM_, BN_, 2), stream, a, what);       \
-    } while (0)
         // 64x64 grids up to three blocks per CU keep the ring too (its 48 KiB leave room for three resident blocks): training batch
         // M = 1024 x N = 1280 x K = 1280 (320 blocks) 31.7 -> ~20 us, training step 29.0 -> 28.0 ms.  AE_GEMM_DEEP64_MAX=256 restores round 1.
         static const int deep64_max = getenv("AE_GEMM_DEEP64_MAX") ? atoi(getenv("AE_GEMM_DEEP64_MAX")) : 768;
         // (a FOURTH ring stage — three tiles in flight, 128 KiB — measured the same on the 8x8-level convs: 41.9 vs 40.4 us; these launches are
         // not latency-bound by ring depth but by LDS bandwidth: 0.75 ds_read_b128 per MFMA x 8 cycles each against 16-cycle MFMAs)
         if (pick == 3) {   // convs only: a dense 128x160 pick was demoted to 128x64 above
-            if constexpr (AMODE == A_CONV3) AE_LAUNCH(128, 160, 2, 2, 256);
+            if constexpr (AMODE == A_CONV3) rc = run_plain<128, 160, AMODE, 2, 2>(lc, glds, grid);
         }
 #ifdef AE_GEMM_ABLATE
-        else if (pick == 0 && glds && lab_abl == 1) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 1>, grid, 512, lds_of(128, 128, 2), stream, a, what);
-        else if (pick == 0 && glds && lab_abl == 2) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 2>, grid, 512, lds_of(128, 128, 2), stream, a, what);
-        else if (pick == 0 && glds && lab_abl == 3) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 3>, grid, 512, lds_of(128, 128, 2), stream, a, what);
-        else if (pick == 0 && glds && lab_abl == 4) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 4>, grid, 512, lds_of(128, 128, 2), stream, a, what);
+        else if (pick == 0 && glds && lab_abl == 1) rc = run_tile<128, 128, AMODE, 4, 2, true, 1, 2, false, 1>(lc, grid, lds_of(128, 128, 2));
+        else if (pick == 0 && glds && lab_abl == 2) rc = run_tile<128, 128, AMODE, 4, 2, true, 1, 2, false, 2>(lc, grid, lds_of(128, 128, 2));
+        else if (pick == 0 && glds && lab_abl == 3) rc = run_tile<128, 128, AMODE, 4, 2, true, 1, 2, false, 3>(lc, grid, lds_of(128, 128, 2));
+        else if (pick == 0 && glds && lab_abl == 4) rc = run_tile<128, 128, AMODE, 4, 2, true, 1, 2, false, 4>(lc, grid, lds_of(128, 128, 2));
 #endif
         else if (pick == 0 && cs_epi_ok && glds) {
-            rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, true, 0, 1>, grid, 512, lds_wa(128, 128), stream, a, what);
+            rc = run_tile<128, 128, AMODE, 4, 2, true, 1, 2, true, 0, 1>(lc, grid, lds_wa(128, 128));
             cs_done = true;
         } else if (pick == 0 && glds && (conv || kt_block >= 3)) {   // (a conv block has at least 8 K tiles: 9 per 64 input channels, split plans keep 8)
             if constexpr (AMODE == A_DENSE) {
-                if (a.xe == 1) rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 2, false, 0, 1, 1>, grid, 512, lds_wa(128, 128), stream, a, what);
-                else if (a.xe) rc = launch_kernel(gemm_kernel<128, 128, A_DENSE, 4, 2, true, 1, 2, false, 0, 1, 2>, grid, 512, lds_wa(128, 128), stream, a, what);
+                if (a.xe == 1) rc = run_tile<128, 128, A_DENSE, 4, 2, true, 1, 2, false, 0, 1, 1>(lc, grid, lds_wa(128, 128));
+                else if (a.xe) rc = run_tile<128, 128, A_DENSE, 4, 2, true, 1, 2, false, 0, 1, 2>(lc, grid, lds_wa(128, 128));
                 xe_done = a.xe != 0;
             }
-            if (!a.xe) rc = launch_kernel(gemm_kernel<128, 128, AMODE, 4, 2, true, 1, 2, false, 0, 1>, grid, 512, lds_wa(128, 128), stream, a, what);
+            if (!a.xe) rc = run_tile<128, 128, AMODE, 4, 2, true, 1, 2, false, 0, 1>(lc, grid, lds_wa(128, 128));
         }
         else if (pick == 0) {
-            if constexpr (AMODE == A_DENSE) AE_LAUNCH(128, 128, 4, 2, 512);   // fewer than three K tiles, or the register-staged loader
-            else rc = launch_kernel(gemm_kernel<128, 128, A_CONV3, 4, 2, false>, grid, 512, lds_of(128, 128, 2), stream, a, what);   // register-staged loader
+            if constexpr (AMODE == A_DENSE) rc = run_plain<128, 128, AMODE, 4, 2>(lc, glds, grid);   // fewer than three K tiles, or the register-staged loader
+            else rc = run_tile<128, 128, A_CONV3, 4, 2, false>(lc, grid, lds_of(128, 128, 2));   // register-staged loader
         } else if (pick == 1) {
-            if constexpr (AMODE == A_DENSE) AE_LAUNCH(128, 64, 4, 2, 512);
-            else AE_LAUNCH(128, 64, 2, 2, 256);
+            if constexpr (AMODE == A_DENSE) rc = run_plain<128, 64, AMODE, 4, 2>(lc, glds, grid);
+            else rc = run_plain<128, 64, AMODE, 2, 2>(lc, glds, grid);
         } else if (deep_pref && glds && !conv && a.splitk <= 1 && grid <= (unsigned)deep64_max && a.K >= 1280) {
             // the same ring for small 64x64 grids (8x8 level, training batches): M = 768 x N = 1280 at K = 1280 / 2560 / 5120:
             // 23.3 -> 16.4, 37.4 -> 23.2, 67.3 -> 38.7 us; lower K thresholds and a fourth stage measured the same
-            if constexpr (AMODE == A_DENSE) rc = launch_kernel(gemm_kernel<64, 64, A_DENSE, 2, 2, true, 1, 3>, grid, 256, lds_of(64, 64, 3), stream, a, what);
-        } else AE_LAUNCH(64, 64, 2, 2, 256);
-#undef AE_LAUNCH
+            if constexpr (AMODE == A_DENSE) rc = run_tile<64, 64, A_DENSE, 2, 2, true, 1, 3>(lc, grid, lds_of(64, 64, 3));
+        } else rc = run_plain<64, 64, AMODE, 2, 2>(lc, glds, grid);
     }
     if (rc) return rc;
     if (a.xe && !xe_done) {
-        // (ops.py asks ae_gemm_ln_plan first, so this is a caller error; ae_gemm_ln_bf16 runs this selection as a query before it launches, so nothing was written)
+        // (ops.py asks the plan first, so this is a caller error; ae_gemm_ln_bf16 runs this selection as a query before it launches, so nothing was written)
         ae_set_error("%s: no %s instantiation for M=%d N=%d K=%d epilogue %d (ae_gemm_ln_plan says which shapes are covered)", what,
                      a.xe == 1 ? "row-statistics" : "LayerNorm-fold", a.M, a.N, a.K, a.epi);
         return AE_ERR_UNSUPPORTED;
     }
-    if (g_plan_query) return 0;
+    if (report) {
+        report->reduce = a.splitk > 1;
+        report->colstats = a.colstats && !cs_done;
+        return 0;
+    }
     if (a.splitk > 1) {
         long nb = ((long)a.M * a.N / 4 + 255) / 256;
         if (nb > 2048) nb = 2048;
@@ -1738,53 +1774,10 @@ struct LnExtras {
     int ln_parts = 0;
     float ln_eps = 0.f;
 };
-int gemm_entry(const void* A, long lda, const void* A2, long lda2, int Ksplit, const void* W, long ldw,
-               void* C, long ldc, int M, int N, int K, const float* bias, const void* residual, long ldr,
-               const float* addvec, long addvec_ld, int rows_per_batch, int epilogue, int out_f32, float* colstats, const LnExtras& x, void* stream);
-}  // namespace
-
-extern "C" int ae_gemm_bf16(const void* A, long lda, const void* A2, long lda2, int Ksplit, const void* W, long ldw,
-                            void* C, long ldc, int M, int N, int K, const float* bias, const void* residual, long ldr,
-                            const float* addvec, long addvec_ld, int rows_per_batch, int epilogue, int out_f32, float* colstats, void* stream) {
-    return gemm_entry(A, lda, A2, lda2, Ksplit, W, ldw, C, ldc, M, N, K, bias, residual, ldr, addvec, addvec_ld, rows_per_batch, epilogue, out_f32, colstats, LnExtras{}, stream);
-}
-
-extern "C" int ae_gemm_ln_bf16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
-                               const void* residual, long ldr, int epilogue, float* rowstats_out, const float* ln_stats, int ln_parts,
-                               const float* ln_colsum, float ln_eps, void* stream) {
-    AE_REQUIRE((rowstats_out != nullptr) != (ln_stats != nullptr), "ae_gemm_ln_bf16: exactly one of rowstats_out (emit) and ln_stats (consume) must be given");
-    AE_REQUIRE(A && W && C && M > 0 && N > 0 && K > 0, "ae_gemm_ln_bf16: null pointer or empty shape");
-    {   // K = 320 (the 64x64 UNet level): the row-panel kernel's fold forms (round 5); AE_ERR_UNSUPPORTED = outside its envelope, the tiled plan decides
-        const int rc = ae_rowpanel_fold_launch(A, lda, W, ldw, C, ldc, M, N, K, bias, residual, ldr, epilogue, rowstats_out, ln_stats, ln_parts, ln_colsum, ln_eps, stream);
-        if (rc != AE_ERR_UNSUPPORTED) return rc;
-    }
-    LnExtras x;
-    x.rowstats_out = rowstats_out; x.ln_stats = ln_stats; x.ln_colsum = ln_colsum; x.ln_parts = ln_parts; x.ln_eps = ln_eps;
-    return gemm_entry(A, lda, nullptr, 0, 0, W, ldw, C, ldc, M, N, K, bias, residual, ldr, nullptr, 0, 0, epilogue, 0, nullptr, x, stream);
-}
-
-extern "C" int ae_gemm_ln_plan(int M, int N, int K, int epilogue, int mode) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % 8 || (mode != 1 && mode != 2) || epilogue < EPI_NONE || epilogue > EPI_RELU) return 0;
-    if (ae_rowpanel_fold_covers(M, N, K, epilogue, mode)) return 1;   // the row-panel kernel's fold forms (K = 320)
-    if (N % 64 || (mode == 1 && (epilogue == EPI_GEGLU || N > 1280)) || (mode == 2 && (K % 64 || K > 1280))) return 0;   // the consumer sums up to 20 slices per row
-    if ((long)M * K * 2 >= (1L << 31) || (long)N * K * 2 >= (1L << 31)) return 0;
-    GemmArgs a{};
-    // (addresses are never dereferenced under g_plan_query: launch_kernel returns before the launch)
-    a.A = a.W = reinterpret_cast<const bf16_t*>(uintptr_t(256)); a.C = reinterpret_cast<void*>(uintptr_t(256));
-    a.M = M; a.N = N; a.K = K; a.Ksplit = K;
-    a.lda = K; a.ldw = K; a.ldc = epilogue == EPI_GEGLU ? N / 2 : N; a.ldav = N;
-    a.epi = epilogue; a.rows_per_batch = 1; a.splitk = 1; a.xe = mode;
-    a.a_bytes = (unsigned)((long)M * K * 2); a.w_bytes = (unsigned)((long)N * K * 2);
-    g_plan_query = 1;
-    const int rc = launch<A_DENSE>(a, nullptr);
-    g_plan_query = 0;
-    return rc == 0 ? 1 : 0;
-}
-
-namespace {
-int gemm_entry(const void* A, long lda, const void* A2, long lda2, int Ksplit, const void* W, long ldw,
-               void* C, long ldc, int M, int N, int K, const float* bias, const void* residual, long ldr,
-               const float* addvec, long addvec_ld, int rows_per_batch, int epilogue, int out_f32, float* colstats, const LnExtras& x, void* stream) {
+// the GemmArgs of a dense launch: the one place they are checked and built, for ae_gemm_bf16 / ae_gemm_ln_bf16 and for the plan query
+int gemm_args(GemmArgs& a, const void* A, long lda, const void* A2, long lda2, int Ksplit, const void* W, long ldw,
+              void* C, long ldc, int M, int N, int K, const float* bias, const void* residual, long ldr,
+              const float* addvec, long addvec_ld, int rows_per_batch, int epilogue, int out_f32, float* colstats, const LnExtras& x) {
     AE_REQUIRE(A && W && C, "ae_gemm_bf16: null pointer");
     if (colstats) AE_REQUIRE(!out_f32 && N % 8 == 0 && ldc % 8 == 0 && (reinterpret_cast<uintptr_t>(colstats) & 15) == 0, "ae_gemm_bf16: column statistics need a bf16 output with N %% 8 == 0 and 16-byte rows");
     AE_REQUIRE(M > 0 && N > 0 && K > 0, "ae_gemm_bf16: M,N,K must be positive (got %d,%d,%d)", M, N, K);
@@ -1802,7 +1795,7 @@ int gemm_entry(const void* A, long lda, const void* A2, long lda2, int Ksplit, c
     }
     if (residual) AE_REQUIRE(ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(residual) & 7) == 0, "ae_gemm_bf16: residual alignment");
     if (addvec) AE_REQUIRE(rows_per_batch > 0, "ae_gemm_bf16: rows_per_batch must be > 0 with addvec");
-    GemmArgs a{};
+    a = GemmArgs{};
     a.A = (const bf16_t*)A; a.A2 = (const bf16_t*)A2; a.W = (const bf16_t*)W; a.C = C;
     a.bias = bias; a.res = (const bf16_t*)residual; a.addvec = addvec;
     a.M = M; a.N = N; a.K = K; a.Ksplit = A2 ? Ksplit : K;
@@ -1828,48 +1821,102 @@ int gemm_entry(const void* A, long lda, const void* A2, long lda2, int Ksplit, c
             AE_REQUIRE(aligned16(x.ln_colsum) && aligned16(bias) && (reinterpret_cast<uintptr_t>(x.ln_stats) & 7) == 0, "ae_gemm_ln_bf16: s / c must be 16-byte aligned, the statistics 8-byte aligned");
             a.xe = 2; a.ln_stats = x.ln_stats; a.ln_colsum = x.ln_colsum; a.ln_parts = x.ln_parts; a.ln_eps = x.ln_eps;
         }
-        // the selection runs once without launching: a shape whose plan has no such epilogue is refused before anything is written
-        g_plan_query = 1;
-        const int rc = launch<A_DENSE>(a, nullptr);
-        g_plan_query = 0;
+    }
+    return 0;
+}
+
+int gemm_entry(const void* A, long lda, const void* A2, long lda2, int Ksplit, const void* W, long ldw,
+               void* C, long ldc, int M, int N, int K, const float* bias, const void* residual, long ldr,
+               const float* addvec, long addvec_ld, int rows_per_batch, int epilogue, int out_f32, float* colstats, const LnExtras& x, void* stream) {
+    GemmArgs a;
+    int rc = gemm_args(a, A, lda, A2, lda2, Ksplit, W, ldw, C, ldc, M, N, K, bias, residual, ldr, addvec, addvec_ld, rows_per_batch, epilogue, out_f32, colstats, x);
+    if (rc) return rc;
+    if (a.xe) {   // the selection runs once without launching: a shape whose plan has no such epilogue is refused before anything is written
+        PlanReport r;
+        rc = launch<A_DENSE>(a, nullptr, &r);
         if (rc) return rc;
     }
     return launch<A_DENSE>(a, (hipStream_t)stream);
 }
 }  // namespace
 
+extern "C" int ae_gemm_bf16(const void* A, long lda, const void* A2, long lda2, int Ksplit, const void* W, long ldw,
+                            void* C, long ldc, int M, int N, int K, const float* bias, const void* residual, long ldr,
+                            const float* addvec, long addvec_ld, int rows_per_batch, int epilogue, int out_f32, float* colstats, void* stream) {
+    return gemm_entry(A, lda, A2, lda2, Ksplit, W, ldw, C, ldc, M, N, K, bias, residual, ldr, addvec, addvec_ld, rows_per_batch, epilogue, out_f32, colstats, LnExtras{}, stream);
+}
+
+extern "C" int ae_gemm_ln_bf16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
+                               const void* residual, long ldr, int epilogue, float* rowstats_out, const float* ln_stats, int ln_parts,
+                               const float* ln_colsum, float ln_eps, void* stream) {
+    AE_REQUIRE((rowstats_out != nullptr) != (ln_stats != nullptr), "ae_gemm_ln_bf16: exactly one of rowstats_out (emit) and ln_stats (consume) must be given");
+    AE_REQUIRE(A && W && C && M > 0 && N > 0 && K > 0, "ae_gemm_ln_bf16: null pointer or empty shape");
+    {   // K = 320 (the 64x64 UNet level): the row-panel kernel's fold forms (round 5); AE_ERR_UNSUPPORTED = outside its envelope, the tiled plan decides
+        const int rc = ae_rowpanel_fold_launch(A, lda, W, ldw, C, ldc, M, N, K, bias, residual, ldr, epilogue, rowstats_out, ln_stats, ln_parts, ln_colsum, ln_eps, stream);
+        if (rc != AE_ERR_UNSUPPORTED) return rc;
+    }
+    LnExtras x;
+    x.rowstats_out = rowstats_out; x.ln_stats = ln_stats; x.ln_colsum = ln_colsum; x.ln_parts = ln_parts; x.ln_eps = ln_eps;
+    return gemm_entry(A, lda, nullptr, 0, 0, W, ldw, C, ldc, M, N, K, bias, residual, ldr, nullptr, 0, 0, epilogue, 0, nullptr, x, stream);
+}
+
+extern "C" int ae_gemm_plan(int M, int N, int K, int epilogue, int Ksplit, int out_f32, int colstats, int ln_mode, int* plan) {
+    AE_REQUIRE(plan && ln_mode >= 0 && ln_mode <= 2, "ae_gemm_plan: null plan or LN mode %d outside 0..2", ln_mode);
+    AE_REQUIRE(M > 0 && N > 0 && K > 0 && K % 8 == 0 && epilogue >= EPI_NONE && epilogue <= EPI_RELU, "ae_gemm_plan: bad shape or epilogue");
+    PlanReport r{};
+    r.rowpanel = ln_mode ? ae_rowpanel_fold_covers(M, N, K, epilogue, ln_mode) : 0;   // the row-panel kernel's fold forms (K = 320)
+    if (r.rowpanel) return plan_out(0, r, plan);
+    AE_REQUIRE(ln_mode != 1 || N <= 1280, "ae_gemm_plan: the consumer of row statistics sums up to 20 slices per row (N = %d)", N);
+    void* const p = kQueryPtr;
+    float* const f = kQueryF32;
+    LnExtras x;
+    if (ln_mode == 1) x.rowstats_out = f;
+    if (ln_mode == 2) { x.ln_stats = f; x.ln_colsum = f; x.ln_parts = K / 64; }
+    GemmArgs a;
+    const int rc = gemm_args(a, p, K, Ksplit > 0 ? p : nullptr, K, Ksplit, p, K, p, epilogue == EPI_GEGLU ? N / 2 : N, M, N, K, ln_mode == 2 ? f : nullptr, nullptr, 0,
+                             nullptr, 0, 0, epilogue, out_f32, colstats ? f : nullptr, x);
+    return plan_out(rc ? rc : launch<A_DENSE>(a, nullptr, &r), r, plan);
+}
+
+extern "C" int ae_gemm_ln_plan(int M, int N, int K, int epilogue, int mode) {
+    int plan[AE_PLAN_INTS];
+    return (mode == 1 || mode == 2) && ae_gemm_plan(M, N, K, epilogue, 0, 0, 0, mode, plan) == 0 ? 1 : 0;
+}
+
 namespace {
 // nearest-x2 upsample + 3x3 conv as four 2x2 convs (GemmArgs::sub2): the 192x320 ping-pong tile where the four parity copies of its tile grid fill whole
 // rounds of the chip (UNet batch 12: the 32x32 -> 64x64 and 16x16 -> 32x32 up-convs), the 8-wave 128x128 weights-ahead tile otherwise.  Both are the
 // instantiations the stride-1 convs of those levels already run (with / without the column statistics for the consuming GroupNorm).
-int launch_sub2(GemmArgs a, hipStream_t stream) {
-    const char* what = "ae_conv3x3_up2_bf16";
+int launch_sub2(GemmArgs a, hipStream_t stream, PlanReport* report = nullptr) {
+    const LaunchCtx lc{a, stream, "ae_conv3x3_up2_bf16", report};
     a.m_fast = (9L * a.N >= 8L * a.M) ? 1 : 0;
     const bool cs = a.colstats != nullptr;
     int rc;
     const long t192 = (a.M % 192 == 0 && a.N % 320 == 0) ? (long)(a.M / 192) * (a.N / 320) * 4 : 0;
     if (t192 > 0 && (double)t192 / (double)(((t192 + 255) / 256) * 256) >= 0.85) {
         const size_t lds = (size_t)(3 * 192 + 2 * 320) * BK * sizeof(bf16_t);
-        if (cs) rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, true, 0, 3>, (unsigned)t192, 512, lds, stream, a, what);
-        else rc = launch_kernel(gemm_kernel<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 3>, (unsigned)t192, 512, lds, stream, a, what);
+        if (cs) rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, true, 0, 3>(lc, t192, lds);
+        else rc = run_tile<192, 320, A_CONV3, 2, 4, true, 1, 2, false, 0, 3>(lc, t192, lds);
     } else {
         const unsigned grid = (unsigned)((long)((a.M + 127) / 128) * ((a.N + 127) / 128) * 4);
         const size_t lds = (size_t)(2 * 128 + 3 * 128) * BK * sizeof(bf16_t);
-        if (cs) rc = launch_kernel(gemm_kernel<128, 128, A_CONV3, 4, 2, true, 1, 2, true, 0, 1>, grid, 512, lds, stream, a, what);
-        else rc = launch_kernel(gemm_kernel<128, 128, A_CONV3, 4, 2, true, 1, 2, false, 0, 1>, grid, 512, lds, stream, a, what);
+        if (cs) rc = run_tile<128, 128, A_CONV3, 4, 2, true, 1, 2, true, 0, 1>(lc, grid, lds);
+        else rc = run_tile<128, 128, A_CONV3, 4, 2, true, 1, 2, false, 0, 1>(lc, grid, lds);
     }
     return rc;
 }
 }  // namespace
 
-extern "C" int ae_conv3x3_up2_bf16(const void* x, const void* w4, const float* bias, void* y, int B, int H, int W, int Cin, int Cout, float* colstats, void* stream) {
+namespace {
+// the GemmArgs of an up-conv launch, checked and built for ae_conv3x3_up2_bf16 and for its plan query
+int up2_args(GemmArgs& a, const void* x, const void* w4, const float* bias, void* y, int B, int H, int W, int Cin, int Cout, float* colstats) {
     AE_REQUIRE(x && w4 && y, "ae_conv3x3_up2_bf16: null pointer");
     AE_REQUIRE(B > 0 && H > 0 && W > 0, "ae_conv3x3_up2_bf16: bad shape B=%d H=%d W=%d", B, H, W);
     AE_REQUIRE(Cin % 64 == 0 && Cout % 8 == 0, "ae_conv3x3_up2_bf16: Cin %% 64 == 0 (whole K tiles per tap) and Cout %% 8 == 0 (row-contiguous stores), got %d -> %d", Cin, Cout);
     AE_REQUIRE(aligned16(x) && aligned16(w4) && aligned16(y), "ae_conv3x3_up2_bf16: pointers must be 16-byte aligned");
     if (colstats) AE_REQUIRE((H * W) % 32 == 0 && (reinterpret_cast<uintptr_t>(colstats) & 15) == 0, "ae_conv3x3_up2_bf16: column statistics are kept per 32-row slab of a sample and parity: H * W = %d must be a multiple of 32", H * W);
     AE_REQUIRE((long)B * H * W * Cin * 2 < (1L << 31) && (long)Cout * 4 * Cin * 2 < (1L << 31) && (long)B * 4 * H * W < (1L << 31), "ae_conv3x3_up2_bf16: operands must be smaller than 2 GiB");
-    GemmArgs a{};
+    a = GemmArgs{};
     a.A = (const bf16_t*)x; a.A2 = nullptr; a.W = (const bf16_t*)w4; a.C = y;
     a.bias = bias; a.res = nullptr; a.addvec = nullptr;
     a.M = B * H * W; a.N = Cout; a.K = 4 * Cin; a.Ksplit = a.K;
@@ -1878,7 +1925,22 @@ extern "C" int ae_conv3x3_up2_bf16(const void* x, const void* w4, const float* b
     a.H = H; a.Wd = W; a.Cin = Cin; a.CinPad = Cin; a.Ho = H; a.Wo = W; a.stride = 1; a.ups = 0;
     a.a_bytes = (unsigned)((long)B * H * W * Cin * 2); a.a2_bytes = 0u; a.w_bytes = (unsigned)((long)Cout * 4 * Cin * 2);
     a.splitk = 1; a.partial = nullptr; a.colstats = colstats; a.kmajor = 0; a.sub2 = 1;
-    return launch_sub2(a, (hipStream_t)stream);
+    return 0;
+}
+}  // namespace
+
+extern "C" int ae_conv3x3_up2_bf16(const void* x, const void* w4, const float* bias, void* y, int B, int H, int W, int Cin, int Cout, float* colstats, void* stream) {
+    GemmArgs a;
+    const int rc = up2_args(a, x, w4, bias, y, B, H, W, Cin, Cout, colstats);
+    return rc ? rc : launch_sub2(a, (hipStream_t)stream);
+}
+
+extern "C" int ae_conv3x3_up2_plan(int B, int H, int W, int Cin, int Cout, int colstats, int* plan) {
+    AE_REQUIRE(plan, "ae_conv3x3_up2_plan: null plan");
+    GemmArgs a;
+    PlanReport r{};
+    const int rc = up2_args(a, kQueryPtr, kQueryPtr, nullptr, kQueryPtr, B, H, W, Cin, Cout, colstats ? kQueryF32 : nullptr);
+    return plan_out(rc ? rc : launch_sub2(a, nullptr, &r), r, plan);
 }
 
 extern "C" long ae_conv3x3_workspace_floats(int B, int H, int W, int Cin, int Cout, int stride, int upsample2x) {
@@ -1890,9 +1952,11 @@ extern "C" long ae_conv3x3_workspace_floats(int B, int H, int W, int Cin, int Co
     return s > 1 ? (long)s * M * Cout : 0;
 }
 
-extern "C" int ae_conv3x3_bf16(const void* x, const void* w, const float* bias, const float* addvec, long addvec_ld,
-                               const void* residual, void* y, int B, int H, int W, int Cin, int Cout, int stride, int upsample2x,
-                               int out_f32, float* workspace, float* colstats, int k_order, void* stream) {
+namespace {
+// the GemmArgs of a conv launch and the tile of its split plan, checked and built for ae_conv3x3_bf16 and for its plan query
+int conv_args(GemmArgs& a, int& split_tile, const void* x, const void* w, const float* bias, const float* addvec, long addvec_ld,
+              const void* residual, void* y, int B, int H, int W, int Cin, int Cout, int stride, int upsample2x,
+              int out_f32, float* workspace, float* colstats, int k_order) {
     AE_REQUIRE(x && w && y, "ae_conv3x3_bf16: null pointer");
     AE_REQUIRE(k_order == 0 || k_order == 1, "ae_conv3x3_bf16: k_order must be 0 (tap, channel) or 1 (64-channel chunk, tap, channel)");
     AE_REQUIRE(k_order == 0 || (Cin % 64 == 0 && !upsample2x), "ae_conv3x3_bf16: the chunk-major K order needs Cin %% 64 == 0 and no upsampling (Cin=%d)", Cin);
@@ -1906,7 +1970,7 @@ extern "C" int ae_conv3x3_bf16(const void* x, const void* w, const float* bias, 
     AE_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y), "ae_conv3x3_bf16: pointers must be 16-byte aligned");
     const int Hv = upsample2x ? 2 * H : H, Wv = upsample2x ? 2 * W : W;
     const int Ho = (Hv + 2 - 3) / stride + 1, Wo = (Wv + 2 - 3) / stride + 1;
-    GemmArgs a{};
+    a = GemmArgs{};
     a.A = (const bf16_t*)x; a.A2 = nullptr; a.W = (const bf16_t*)w; a.C = y;
     a.bias = bias; a.res = (const bf16_t*)residual; a.addvec = addvec;
     const int CinPad = (Cin + BK - 1) / BK * BK;  // weights are packed [Cout, 9*CinPad], zero padded per tap
@@ -1916,9 +1980,31 @@ extern "C" int ae_conv3x3_bf16(const void* x, const void* w, const float* bias, 
     a.H = H; a.Wd = W; a.Cin = Cin; a.CinPad = CinPad; a.Ho = Ho; a.Wo = Wo; a.stride = stride; a.ups = upsample2x;
     a.a_bytes = (unsigned)((long)B * H * W * Cin * 2); a.a2_bytes = 0u; a.w_bytes = (unsigned)((long)Cout * 9 * CinPad * 2);
     AE_REQUIRE((long)B * H * W * Cin * 2 < (1L << 31) && (long)Cout * 9 * CinPad * 2 < (1L << 31), "ae_conv3x3_bf16: operands must be smaller than 2 GiB");
-    a.splitk = workspace ? make_plan(a.M, a.N, a.K, true).splitk : 1;  // without a workspace the kernel runs unsplit
+    const Plan plan = workspace ? make_plan(a.M, a.N, a.K, true) : Plan{0, 1};  // without a workspace the kernel runs unsplit
+    a.splitk = plan.splitk;
+    split_tile = plan.tile;
     a.partial = workspace;
     a.colstats = colstats;
     a.kmajor = k_order;
-    return launch<A_CONV3>(a, (hipStream_t)stream);
+    return 0;
+}
+}  // namespace
+
+extern "C" int ae_conv3x3_bf16(const void* x, const void* w, const float* bias, const float* addvec, long addvec_ld,
+                               const void* residual, void* y, int B, int H, int W, int Cin, int Cout, int stride, int upsample2x,
+                               int out_f32, float* workspace, float* colstats, int k_order, void* stream) {
+    GemmArgs a;
+    int split_tile;
+    const int rc = conv_args(a, split_tile, x, w, bias, addvec, addvec_ld, residual, y, B, H, W, Cin, Cout, stride, upsample2x, out_f32, workspace, colstats, k_order);
+    return rc ? rc : launch<A_CONV3>(a, (hipStream_t)stream, nullptr, split_tile);
+}
+
+extern "C" int ae_conv3x3_plan(int B, int H, int W, int Cin, int Cout, int stride, int upsample2x, int out_f32, int workspace, int colstats, int k_order, int* plan) {
+    AE_REQUIRE(plan, "ae_conv3x3_plan: null plan");
+    GemmArgs a;
+    int split_tile;
+    PlanReport r{};
+    const int rc = conv_args(a, split_tile, kQueryPtr, kQueryPtr, nullptr, nullptr, 0, nullptr, kQueryPtr, B, H, W, Cin, Cout, stride, upsample2x, out_f32,
+                             workspace ? kQueryF32 : nullptr, colstats ? kQueryF32 : nullptr, k_order);
+    return plan_out(rc ? rc : launch<A_CONV3>(a, nullptr, &r, split_tile), r, plan);
 }

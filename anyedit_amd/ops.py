@@ -5,6 +5,7 @@ Activations are channels-last bf16: [rows, C] with rows = B*H*W.
 """
 import torch
 
+import collections
 import ctypes
 import os
 import threading
@@ -200,15 +201,54 @@ def im2col3x3_c8(x, B, H, W):
 _CONV_KMAJOR = int(os.environ.get("AE_CONV_KMAJOR", "2"))  # tuning knob: 0 off, 1 un-split 192x320 plan, 2 + its split-K form, 3 every eligible conv, 4 un-split 192x320 and 128x128 plans
 
 
+# --------------------------------------------------------------------------- launch plans: the library says what it would run
+Plan = collections.namedtuple("Plan", "BM BN AMODE WAVES_M WAVES_N GLDS WAVES_K STAGES CS LAB WA XE grid threads lds splitk reduce colstats rowpanel")
+_PLANS = {}
+
+
+def _plan(query, *args):
+    """The plan[] of `ae_gemm_plan` / `ae_conv3x3_plan` / `ae_conv3x3_up2_plan` (include/anyedit_hip.h: the library's own launch selection, run
+    without launching; host only), cached per argument tuple — the library latches its AE_* knobs once per process, so an answer never changes.
+    None: the launch would be refused."""
+    key = (query,) + args
+    if key not in _PLANS:
+        buf = (ctypes.c_int * len(Plan._fields))()
+        _PLANS[key] = Plan(*buf) if getattr(lib, query)(*args, buf) == 0 else None
+    return _PLANS[key]
+
+
+def gemm_plan(M, N, K, epilogue=EPI_NONE, Ksplit=0, out_f32=False, colstats=False, ln_mode=0):
+    """What `gemm` (ln_mode 0) / `gemm_ln`'s launch (1 emits row statistics, 2 consumes them) would run."""
+    return _plan("ae_gemm_plan", M, N, K, epilogue, Ksplit, int(out_f32), int(colstats), ln_mode)
+
+
+def conv_plan(B, H, W, Cin, Cout, stride=1, upsample2x=0, out_f32=False, colstats=False, k_order=0):
+    """What `conv3x3` would run (it always offers the split-K workspace)."""
+    return _plan("ae_conv3x3_plan", B, H, W, Cin, Cout, stride, int(upsample2x), int(out_f32), 1, int(colstats), int(k_order))
+
+
+def up2_plan(B, H, W, Cin, Cout, colstats=False):
+    return _plan("ae_conv3x3_up2_plan", B, H, W, Cin, Cout, int(colstats))
+
+
+def plan_label(p):
+    """"192x320", "192x320,splitK", "128x128,ring3", "128x160", ...: tile, three-stage ring, split-K — how the profiler rows name a plan"""
+    return f"{p.BM}x{p.BN}" + (",ring3" if p.STAGES == 3 else "") + (",splitK" if p.splitk > 1 else "")
+
+
 def conv_k_order(M, Cin, Cout, stride=1, upsample2x=False):
-    """Which packed K order `conv3x3` should be given for this launch (the planner's mirror): the chunk-major order where the 192x320 tile
-    runs (64x64 UNet level at batch >= 12: a block's nine tap windows are then re-read from L2 instead of the MALL), the tap-major order
-    elsewhere (measured slower there) and always under the tape (the backward passes use rotated tap-major packs)."""
-    if _CONV_KMAJOR == 0 or upsample2x or Cin % 64 != 0 or (_TAPE is not None and _TAPE.active) or os.environ.get("AE_GEMM_GLDS", "1") == "0":
+    """Which packed K order `conv3x3` should be given for this launch: the chunk-major order where the library plans the 192x320 tile
+    (64x64 UNet level at batch >= 12: a block's nine tap windows are then re-read from L2 instead of the MALL), the tap-major order
+    elsewhere (measured slower there) and always under the tape (the backward passes use rotated tap-major packs).
+    M: output rows.  Tile and split of a conv depend on the map's size only through M, so the question is put for M one-pixel samples."""
+    if _CONV_KMAJOR == 0 or upsample2x or Cin % 64 != 0 or (_TAPE is not None and _TAPE.active):
+        return 0
+    p = conv_plan(M, 1, 1, Cin, Cout, stride)
+    if p is None or not p.GLDS:   # the chunk-major order exists in the LDS-DMA loader only
         return 0
     if _CONV_KMAJOR == 3:
         return 1
-    label = _tile_label(M, Cout, True, 9 * Cin, False, True)
+    label = plan_label(p)
     if _CONV_KMAJOR == 4:   # (A/B only) the un-split plans of the 64x64 and 32x32 levels
         return 1 if label in ("192x320", "128x128") else 0
     return 1 if (label == "192x320" or (_CONV_KMAJOR >= 2 and label == "192x320,splitK")) else 0
@@ -365,23 +405,18 @@ def gemm(a, w, bias=None, residual=None, addvec=None, rows_per_batch=0, epilogue
 
 # --------------------------------------------------------------------------- LayerNorm folded into the consuming GEMM
 _LN_FOLD = os.environ.get("AE_LN_FOLD", "1") != "0"  # tuning knob (A/B): 0 = a LayerNorm launch in front of every K = 640 / 1280 projection
-_LN_PLAN = {}
 
 
 def ln_fold_plan(M, N, K, epilogue, mode):
     """True where the tile plan `gemm` takes for [M, K] x [N, K]^T carries the row-statistics epilogue (mode 1: this GEMM PRODUCES the
-    rows a LayerNorm reads) or the LayerNorm-fold epilogue (mode 2: this GEMM CONSUMES the LayerNorm) — `ae_gemm_ln_plan`, cached per
+    rows a LayerNorm reads) or the LayerNorm-fold epilogue (mode 2: this GEMM CONSUMES the LayerNorm) — `gemm_plan`, cached per
     shape.  Never while the training tape records (its LayerNorm keeps what the backward pass needs)."""
     if not _LN_FOLD or (_TAPE is not None and _TAPE.active):
         return False
-    key = (M, N, K, epilogue, mode)
-    r = _LN_PLAN.get(key)
-    if r is None:
-        # shapes of the row-panel kernel (K = 320, the 64x64 level): round 5 gave that kernel the fold forms too (AE_RP_FOLD, read by the library: its
-        # plan query says yes for them); with the row-panel kernel switched off (AE_GEMM_ROWPANEL=0, A/B) the tiled plan answers
-        r = _LN_PLAN[key] = bool(lib.ae_gemm_ln_plan(M, N, K, epilogue, mode)) and \
-            (_ROWPANEL or not lib.ae_ln_gemm_supported(M, N, K, epilogue) or os.environ.get("AE_RP_FOLD", "1") == "0")
-    return r
+    # shapes of the row-panel kernel (K = 320, the 64x64 level): round 5 gave that kernel the fold forms too (the plan says where they take the
+    # launch); no fold there with the row-panel kernel switched off (AE_GEMM_ROWPANEL=0, A/B)
+    p = gemm_plan(M, N, K, epilogue, ln_mode=mode)
+    return p is not None and (_ROWPANEL or not p.rowpanel)
 
 
 def rowstats_buffer(M, N, device):
@@ -2230,66 +2265,6 @@ class OpProfiler:
 _PROF = None
 
 
-def _tile_label(M, N, conv=False, K=0, geglu=False, dma_ok=True, xe2=False):
-    """Mirror of the tile choice in csrc/gemm_conv.hip::launch / make_plan (for labelling only)."""
-    if conv and dma_ok and _conv_t320_split(M, N, K):
-        return "192x320,splitK"
-    if dma_ok and N % 320 == 0 and (conv or K >= 640):   # convs, GEGLU GEMMs with K >= 640 and (round 3) the other dense GEMMs with K >= 640
-        tm = -(-M // 192)
-        t = tm * (N // 320)
-        fill = t / (-(-t // 256) * 256) * (M / (tm * 192))
-        if fill >= 0.85 and not (conv and _conv_splitk(M, N, K) > 1):
-            return "192x320"
-        t128 = -(-M // 128) * -(-N // 128)
-        if xe2 and not conv and not geglu and 0.74 <= fill < 0.85 and t128 / (-(-t128 // 512) * 512) <= 0.72 and os.environ.get("AE_GEMM_T320_XE", "1") != "0":
-            return "192x320"   # round 5: a LayerNorm-fold launch whose 128x128 grid leaves a bad tail (qkv of the 16x16 level)
-    if conv and _conv_splitk(M, N, K) > 1:
-        return "128x128,splitK"
-    if conv and N % 160 == 0 and N % 128 != 0 and -(-M // 128) * (N // 160) >= 256:
-        return "128x160"
-    if not conv and not geglu and dma_ok and N % 128 == 0 and K >= 1280 and 128 <= -(-M // 128) * (N // 128) <= 256:
-        return "128x128,ring3"  # three-stage ring, one block per CU
-    if not conv and not geglu and dma_ok and N % 128 == 0 and K >= 2560 and -(-M // 128) * (N // 128) > 256 and 128 <= -(-M // 192) * (N // 128) <= 256:
-        return "192x128,ring3"
-    for bm, bn in ((128, 128), (128, 64), (64, 64)):
-        tm, tn = -(-M // bm), -(-N // bn)
-        if tm * tn >= 256 and tn * bn / N <= 1.10:
-            if bm == 64 and not conv and dma_ok and K >= 1280 and tm * tn <= 768:
-                return "64x64,ring3"
-            return f"{bm}x{bn}"
-    if not conv and dma_ok and K >= 1280 and -(-M // 64) * -(-N // 64) <= 768:
-        return "64x64,ring3"
-    return "64x64"
-
-
-def _conv_t320_split(M, N, K):
-    """split count of the 192x320 split-K plan (16x16-level convs), 0 when it does not apply (make_plan, tile id 4)."""
-    kt = -(-K // 64)
-    knob = int(os.environ.get("AE_CONV_T320_SPLITK", "3"))   # mirror of make_plan's knob: 2 = grids of 32..64 tiles, 3 (default, round 5) = + 65..128 tiles with >= 180 K tiles, 1 = every grid up to 128
-    hi = 64 if (knob == 2 or (knob == 3 and kt < 180)) else 128
-    if knob and N % 320 == 0 and M % 192 == 0 and 32 <= (M // 192) * (N // 320) <= hi:
-        s_ = min(256 // ((M // 192) * (N // 320)), 8)
-        while s_ > 1 and kt // s_ < 16:
-            s_ -= 1
-        return s_ if s_ >= 2 else 0
-    return 0
-
-
-def _conv_splitk(M, N, K):
-    kt = -(-K // 64)
-    if _conv_t320_split(M, N, K):
-        return _conv_t320_split(M, N, K)
-    t128 = -(-M // 128) * -(-N // 128)
-    picked_big = any(-(-M // bm) * -(-N // bn) >= 256 and -(-N // bn) * bn / N <= 1.10 for bm, bn in ((128, 128),))
-    is160 = N % 160 == 0 and N % 128 != 0 and -(-M // 128) * (N // 160) >= 256
-    if kt < 32 or picked_big or is160:
-        return 1
-    if -(-N // 128) * 128 / N <= 1.10 and t128 < 256:
-        s_ = min(-(-480 // t128), int(os.environ.get("AE_CONV_SPLIT_MAX", "8")), kt // 8)
-        return s_ if s_ >= 2 else 1
-    return 1
-
-
 def _wrap_profiled(fn, label_fn):
     def wrapped(*args, **kwargs):
         if _PROF is None:
@@ -2313,15 +2288,16 @@ def _gemm_label(_r, a, w, bias=None, residual=None, addvec=None, rows_per_batch=
     nb = 2 * (M * K + N * K) + _r.numel() * _r.element_size() + (2 * M * N if residual is not None else 0)
     if a2 is None and addvec is None and not out_f32 and _rowpanel_ok(a, w, _r, residual, M, N, K, epilogue):
         return f"gemm_rowpanel_kernel<K=320{',geglu' if epilogue == EPI_GEGLU else ''}>|M={M} N={N}", 2.0 * M * N * K, nb
-    return f"gemm_kernel<{_tile_label(M, N, False, K, epilogue == EPI_GEGLU, K % 64 == 0 and a2 is None)},dense>|M={M} N={N} K={K}", 2.0 * M * N * K, float(nb)
+    p = gemm_plan(M, N, K, epilogue, a.shape[1] if a2 is not None else 0, out_f32, _.get("colstats") is not None)
+    return f"gemm_kernel<{plan_label(p)},dense>|M={M} N={N} K={K}", 2.0 * M * N * K, float(nb), 1 + p.colstats
 
 
 def _conv_label(_r, x, w, bias, B, H, W, addvec=None, residual=None, stride=1, upsample2x=False, out_f32=False, **_):
     y = _r[0]
     M, Cout, Cin = y.shape[0], w.shape[0], x.shape[1]
     nb = 2 * (x.numel() + 9 * Cin * Cout) + y.numel() * y.element_size() + (2 * y.numel() if residual is not None else 0)
-    tl = _tile_label(M, Cout, True, 9 * (-(-Cin // 64) * 64), False, Cin % 64 == 0)
-    return f"gemm_kernel<{tl},conv3x3>|M={M} Cin={Cin} Cout={Cout} s{stride}{'u' if upsample2x else ''}", 2.0 * M * Cout * 9 * Cin, float(nb), (2 if "splitK" in tl else 1)
+    p = conv_plan(B, H, W, Cin, Cout, stride, upsample2x, out_f32, _.get("colstats") is not None, _.get("k_order", 0))
+    return f"gemm_kernel<{plan_label(p)},conv3x3>|M={M} Cin={Cin} Cout={Cout} s{stride}{'u' if upsample2x else ''}", 2.0 * M * Cout * 9 * Cin, float(nb), 1 + p.reduce + p.colstats
 
 
 def _attn_label(_r, q, k, v, B, H, Nq, Nk, D, *a, **kw):
@@ -2359,17 +2335,16 @@ def _ln_gemm_label(_r, x, w, bias, residual, gamma, beta, eps, epilogue, o, M, N
 def _gemm_ln_label(_r, a, w, bias, residual, epilogue, out, M, N, K, rowstats_out, ln_stats, nparts, ln_colsum, eps):
     nb = 2 * (M * K + N * K) + _r.numel() * 2 + (2 * M * N if residual is not None else 0)
     tag = "rowstats" if rowstats_out is not None else "LNfold"
-    if _ROWPANEL and os.environ.get("AE_RP_FOLD", "1") != "0" and lib.ae_ln_gemm_supported(M, N, K, epilogue) and (rowstats_out is None or epilogue == EPI_NONE):
-        # round 5: the K = 320 shapes run the row-panel kernel's fold forms (ae_gemm_ln_bf16 forwards them)
+    p = gemm_plan(M, N, K, epilogue, ln_mode=1 if rowstats_out is not None else 2)
+    if p.rowpanel:   # round 5: the K = 320 shapes run the row-panel kernel's fold forms (ae_gemm_ln_bf16 forwards them)
         return f"gemm_rowpanel_kernel<K=320,{tag}{',geglu' if epilogue == EPI_GEGLU else ''}>|M={M} N={N}", 2.0 * M * N * K, nb
-    return f"gemm_kernel<{_tile_label(M, N, False, K, epilogue == EPI_GEGLU, True, xe2=rowstats_out is None)},dense,{tag}>|M={M} N={N} K={K}", 2.0 * M * N * K, float(nb)
+    return f"gemm_kernel<{plan_label(p)},dense,{tag}>|M={M} N={N} K={K}", 2.0 * M * N * K, float(nb)
 
 
 def _up2_label(_r, x, w4, bias, B, H, W, **_):
     y = _r[0]
-    M, Cout, Cin = x.shape[0], w4.shape[1], x.shape[1]
-    t192 = (M // 192) * (Cout // 320) * 4 if (M % 192 == 0 and Cout % 320 == 0) else 0
-    tl = "192x320" if t192 and t192 / (-(-t192 // 256) * 256) >= 0.85 else "128x128"
+    Cout, Cin = w4.shape[1], x.shape[1]
+    tl = plan_label(up2_plan(B, H, W, Cin, Cout, _.get("colstats") is not None))
     nb = 2 * (x.numel() + 16 * Cin * Cout) + 2 * y.numel()
     # FLOP: the 2x2 form's own count (4 taps per output pixel); the gather form it replaces spends 9/4 of it for the same function
     return f"gemm_kernel<{tl},conv3x3,up2x2>|M={y.shape[0]} Cin={Cin} Cout={Cout}", 2.0 * y.shape[0] * Cout * 4 * Cin, float(nb)

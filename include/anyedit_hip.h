@@ -123,6 +123,21 @@ int ae_conv3x3_bf16(const void* x, const void* w, const float* bias, const float
 int ae_conv3x3_up2_bf16(const void* x, const void* w4, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
                         float* colstats, void* stream);
 
+/* Launch plans: what the three entry points above would run for the given scalar arguments — the library's own selection code, run without
+ * launching.  Host only: no GPU call, callable without a device.  0 and plan[0 .. AE_PLAN_INTS) filled, or the error the launch would return.
+ *   plan[0..11]  the template arguments of the gemm_kernel instantiation: BM, BN, AMODE (0 dense, 1 conv), WAVES_M, WAVES_N, GLDS, WAVES_K, STAGES, CS,
+ *                LAB, WA, XE (as the kernel's demangled name spells them);
+ *   plan[12..15] grid, threads per block, dynamic LDS bytes, split-K factor;
+ *   plan[16..17] 1 where the split-K reduce / the stand-alone column-statistics kernel follows;
+ *   plan[18]     dense, ln_mode != 0 only: 1 = the row-panel kernel's fold forms take the launch instead (plan[0..17] are then zero).
+ * Arguments that are pointers at the launch are flags here (workspace / colstats: given or not); every pointer counts as well aligned.
+ *   ae_gemm_plan: Ksplit 0 = one source; ln_mode 0 = ae_gemm_bf16, 1 / 2 = ae_gemm_ln_bf16 emitting / consuming row statistics.                */
+#define AE_PLAN_INTS 19
+int ae_gemm_plan(int M, int N, int K, int epilogue, int Ksplit, int out_f32, int colstats, int ln_mode, int* plan);
+int ae_conv3x3_plan(int B, int H, int W, int Cin, int Cout, int stride, int upsample2x, int out_f32, int workspace, int colstats, int k_order,
+                    int* plan);
+int ae_conv3x3_up2_plan(int B, int H, int W, int Cin, int Cout, int colstats, int* plan);
+
 /* GroupNorm32 (+SiLU) (util.py:217-219 eps 1e-5; attention.py:88-89 eps 1e-6); input may be the channel-concat [x | x2].
  * workspace: fp32, ae_groupnorm_workspace_floats(B,HW,C,groups) elements.  act: 0 none, 1 SiLU.
  * counters: optional int32[B], ZERO on entry and zero again on exit, not shared with a launch running concurrently on another

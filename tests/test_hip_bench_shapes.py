@@ -6,7 +6,7 @@ configs[2] (8 images per rank = UNet batch 24).  At those batches the library pi
 buffers all depend on M), so every one of them is compared here with an oracle VALUE, not with a property:
 
   * the dominant kernel instance `gemm_kernel<192x320,conv3x3>` on the four 64x64-level shapes of the UNet vs CPU `F.conv2d`
-    (openaimodel.py:254-274, :108-118), with the plan asserted through the label mirror;
+    (openaimodel.py:254-274, :108-118), with the plan asserted through the library's plan query;
   * the whole UNet at batch 12 and batch 24 vs the fp32 oracle, sample by sample, with the bf16-storage control
     (openaimodel.py:754-786);
   * SAM ViT-H (32 blocks, 1024x1024) vs `oracle.sam_ref.image_encoder` (image_encoder.py:106-116);
@@ -48,7 +48,7 @@ def test_conv3x3_bench_plan_vs_conv2d(B, H, W, Cin, Cout, ups):
     emb = torch.randn(B, Cout, generator=g)
     Ho, Wo = (2 * H, 2 * W) if ups else (H, W)
     M = B * Ho * Wo
-    assert ops._tile_label(M, Cout, True, 9 * Cin, False, True) == "192x320", "this shape must run the un-split 192x320 plan"
+    assert ops.plan_label(ops.conv_plan(B, H, W, Cin, Cout, upsample2x=ups)) == "192x320", "this shape must run the un-split 192x320 plan"
     assert ops.lib.ae_conv3x3_workspace_floats(B, H, W, Cin, Cout, 1, int(ups)) == 0          # un-split: no partials
     xi = F.interpolate(x, scale_factor=2, mode="nearest") if ups else x
     ref = F.conv2d(xi, w, bias, padding=1) + emb[:, :, None, None]
@@ -85,7 +85,8 @@ def test_conv3x3_long_k_32x32_level_takes_the_split_192x320_plan(Cin):
     bias = torch.randn(Cout, generator=g)
     emb = torch.randn(B, Cout, generator=g)
     M = B * H * W
-    assert ops._tile_label(M, Cout, True, 9 * Cin, False, True) == "192x320,splitK" and ops._conv_t320_split(M, Cout, 9 * Cin) == 2
+    plan = ops.conv_plan(B, H, W, Cin, Cout)
+    assert ops.plan_label(plan) == "192x320,splitK" and plan.splitk == 2
     assert ops.lib.ae_conv3x3_workspace_floats(B, H, W, Cin, Cout, 1, 0) == 2 * M * Cout
     assert ops.conv_k_order(M, Cin, Cout) == 1
     ref = F.conv2d(x, w, bias, padding=1) + emb[:, :, None, None]

@@ -1,8 +1,11 @@
 """CPU tests of the host side: C-ABI exports, constructor/state-dict parity with the reference, schedule mirrors,
 weight packing.  No compute calls (no GPU here)."""
 import ctypes
+import json
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -337,19 +340,66 @@ def test_create_model_from_reference_style_yaml(tmp_path):
     assert (sum(p.numel() for p in cnet.parameters()), len(cnet.state_dict())) == (364_228_384, 340)
 
 
-def test_python_plan_mirror_matches_the_library():
-    """ops._conv_splitk (used only to LABEL profiler rows with the kernel that will run) must agree with the launch plan inside the
-    library; ae_conv3x3_workspace_floats is host-only and returns splitk * M * Cout (0 when unsplit), so it can be checked without a GPU."""
+# conv plans "label/split" of the library at B x hw (3x3, stride 1) for the nine (Cin, Cout) of _PLAN_CONVS, and LayerNorm-fold / dense plans: what the
+# parent commit's hand-written Python copy of the planner answered for these shapes (every one agreed with the library), kept as literals
+_PLAN_CONVS = ((320, 320), (640, 640), (1280, 1280), (2560, 1280), (1920, 640), (960, 320), (640, 1280), (8, 320), (320, 4))
+_PLAN_TABLE = {
+    (1, 8): "64x64/1 128x128,splitK/8 128x128,splitK/8 128x128,splitK/8 128x128,splitK/8 64x64/1 128x128,splitK/8 64x64/1 64x64/1",
+    (1, 16): "64x64/1 128x128,splitK/8 128x128,splitK/8 128x128,splitK/8 128x128,splitK/8 64x64/1 128x128,splitK/8 64x64/1 64x64/1",
+    (1, 32): "64x64/1 128x128,splitK/8 128x128,splitK/6 128x128,splitK/6 128x128,splitK/8 64x64/1 128x128,splitK/6 64x64/1 64x64/1",
+    (1, 64): "64x64/1 128x128,splitK/3 128x128/1 128x128/1 128x128,splitK/3 64x64/1 128x128/1 64x64/1 64x64/1",
+    (3, 8): "64x64/1 128x128,splitK/8 128x128,splitK/8 128x128,splitK/8 128x128,splitK/8 64x64/1 128x128,splitK/8 64x64/1 64x64/1",
+    (3, 16): "64x64/1 128x128,splitK/8 128x128,splitK/8 128x128,splitK/8 128x128,splitK/8 64x64/1 128x128,splitK/8 64x64/1 64x64/1",
+    (3, 32): "64x64/1 192x320,splitK/5 192x320,splitK/4 192x320,splitK/4 192x320,splitK/8 64x64/1 192x320,splitK/4 64x64/1 64x64/1",
+    (3, 64): "192x320,splitK/2 128x128/1 192x320/1 192x320/1 192x320,splitK/2 192x320,splitK/4 192x320/1 128x64/1 64x64/1",
+    (4, 8): "64x64/1 128x128,splitK/8 128x128,splitK/8 128x128,splitK/8 128x128,splitK/8 64x64/1 128x128,splitK/8 64x64/1 64x64/1",
+    (4, 16): "64x64/1 128x128,splitK/8 128x128,splitK/6 128x128,splitK/6 128x128,splitK/8 64x64/1 128x128,splitK/6 64x64/1 64x64/1",
+    (4, 32): "64x64/1 128x128,splitK/3 128x128/1 128x128/1 128x128,splitK/3 64x64/1 128x128/1 64x64/1 64x64/1",
+    (4, 64): "128x160/1 128x128/1 128x128/1 128x128/1 128x128/1 128x160/1 128x128/1 128x160/1 64x64/1",
+    (12, 8): "64x64/1 128x128,splitK/8 128x128,splitK/8 128x128,splitK/8 128x128,splitK/8 64x64/1 128x128,splitK/8 64x64/1 64x64/1",
+    (12, 16): "64x64/1 192x320,splitK/5 192x320,splitK/4 192x320,splitK/4 192x320,splitK/8 64x64/1 192x320,splitK/4 64x64/1 64x64/1",
+    (12, 32): "192x320,splitK/2 128x128/1 192x320/1 192x320/1 192x320,splitK/2 192x320,splitK/4 192x320/1 128x64/1 64x64/1",
+    (12, 64): "192x320/1 192x320/1 192x320/1 192x320/1 192x320/1 192x320/1 192x320/1 128x160/1 64x64/1",
+}
+# (M, N, K, epilogue, ln_mode) -> label; "rowpanel": the row-panel kernel's fold forms take the launch; None: no such epilogue on the plan, the launch is refused
+_PLAN_DENSE = {
+    (12288, 640, 640, 0, 1): "128x128", (12288, 1920, 640, 0, 2): "128x128", (12288, 640, 640, 0, 2): "128x128", (12288, 5120, 640, 2, 2): "192x320",
+    (3072, 1280, 1280, 0, 1): "128x128,ring3", (3072, 3840, 1280, 0, 2): "192x320", (3072, 1280, 1280, 0, 2): "128x128,ring3", (3072, 10240, 1280, 2, 2): "192x320",
+    (49152, 960, 320, 0, 2): "rowpanel", (49152, 320, 320, 0, 2): "rowpanel", (49152, 320, 320, 0, 1): "rowpanel", (49152, 2560, 320, 2, 2): "rowpanel",
+    (768, 1280, 1280, 0, 1): None, (49152, 2560, 320, 2, 1): None, (49152, 640, 640, 2, 1): None, (49152, 600, 640, 0, 1): None,
+    (12288, 640, 640, 0, 0): "128x128", (3072, 1280, 1280, 0, 0): "128x128,ring3", (768, 1280, 1280, 0, 0): "64x64,ring3", (49152, 320, 1280, 0, 0): "192x320",
+    # N % 160 == 0, N % 128 != 0, >= 256 tiles of 128x160: pick_tile answers 128x160, which a dense launch demotes to 128x64 (the Python copy said 128x128)
+    (8192, 960, 320, 0, 0): "128x64",
+}
+
+
+def test_launch_plan_labels_are_pinned():
+    """The library's launch-plan queries (host only: its own selection code, run without launching) over the UNet's conv grid and the dense /
+    LayerNorm-fold shapes of the bench batch: label and split-K factor as literals, the split equal to what ae_conv3x3_workspace_floats sizes,
+    and the launches behind a call (split-K reduce, stand-alone column statistics) as the report counts them."""
     from anyedit_amd import ops
     from anyedit_amd._lib import lib
-    for B in (1, 3, 4, 12):
-        for hw in (8, 16, 32, 64):
-            for cin, cout in ((320, 320), (640, 640), (1280, 1280), (2560, 1280), (1920, 640), (960, 320), (640, 1280), (8, 320), (320, 4)):
-                M = B * hw * hw
-                ws = lib.ae_conv3x3_workspace_floats(B, hw, hw, cin, cout, 1, 0)
-                s_lib = ws // (M * cout) if ws else 1
-                cin_pad = (cin + 63) // 64 * 64
-                assert ops._conv_splitk(M, cout, 9 * cin_pad) == s_lib, (B, hw, cin, cout, s_lib)
+    for (B, hw), row in _PLAN_TABLE.items():
+        for (cin, cout), want in zip(_PLAN_CONVS, row.split()):
+            M = B * hw * hw
+            p = ops.conv_plan(B, hw, hw, cin, cout)
+            assert f"{ops.plan_label(p)}/{p.splitk}" == want, (B, hw, cin, cout)
+            ws = lib.ae_conv3x3_workspace_floats(B, hw, hw, cin, cout, 1, 0)
+            assert (ws // (M * cout) if ws else 1) == p.splitk and p.reduce == (p.splitk > 1), (B, hw, cin, cout)
+            assert p.threads == 64 * p.WAVES_M * p.WAVES_N * p.WAVES_K and p.AMODE == 1 and p.GLDS == (cin % 64 == 0) and not p.colstats
+            if cout % 8 == 0:   # column statistics: from the epilogue (CS) or from the stand-alone kernel behind it, never both, never under a split
+                q = ops.conv_plan(B, hw, hw, cin, cout, colstats=True)
+                assert (q.BM, q.BN, q.splitk) == (p.BM, p.BN, p.splitk) and q.CS + q.colstats == 1 and not (q.CS and q.splitk > 1), (B, hw, cin, cout)
+    for (M, N, K, epi, mode), want in _PLAN_DENSE.items():
+        p = ops.gemm_plan(M, N, K, epi, ln_mode=mode)
+        assert (None if p is None else "rowpanel" if p.rowpanel else ops.plan_label(p)) == want, (M, N, K, epi, mode)
+        if mode:
+            assert lib.ae_gemm_ln_plan(M, N, K, epi, mode) == (want is not None)
+            assert p is None or p.rowpanel or p.XE == mode
+    # the decoder's two-source skip 1x1 convs keep the LDS-DMA loader while both K parts are whole K tiles (the Python copy labelled them as if they lost it)
+    assert ops.plan_label(ops.gemm_plan(49152, 320, 960, Ksplit=640)) == "192x320" and ops.plan_label(ops.gemm_plan(3072, 1280, 1920, Ksplit=1280)) == "128x128,ring3"
+    assert ops.plan_label(ops.gemm_plan(768, 1280, 2560, Ksplit=1280)) == "64x64,ring3" and not ops.gemm_plan(768, 1280, 2560, Ksplit=1288).GLDS
+    assert ops.plan_label(ops.up2_plan(12, 32, 32, 640, 640)) == "192x320" and ops.plan_label(ops.up2_plan(3, 16, 24, 640, 640)) == "128x128"
 
 
 def test_layernorm_fold_plan_follows_the_tile_plan(monkeypatch):
@@ -463,8 +513,11 @@ def test_conv_k_order_follows_the_tile_plan(monkeypatch):
     for channel counts that are not multiples of 64 and under the training tape.  Knob 1 (round 3's rule) drops the split-K half, knob 0 is
     tap-major everywhere.  VERDICT r4: the test used to skip itself unless the knob was 1 — at the shipped default nothing checked the rule."""
     from anyedit_amd import ops
-    monkeypatch.delenv("AE_GEMM_GLDS", raising=False)
-    assert int(__import__("os").environ.get("AE_CONV_KMAJOR", "2")) == ops._CONV_KMAJOR
+    assert int(os.environ.get("AE_CONV_KMAJOR", "2")) == ops._CONV_KMAJOR
+
+    def t320_split(B, hw, cin, cout):   # split count of the 192x320 split-K plan, 0 where another plan runs
+        p = ops.conv_plan(B, hw, hw, cin, cout)
+        return p.splitk if (p.BM, p.BN) == (192, 320) and p.splitk > 1 else 0
     for knob in (2, 1, 0):
         monkeypatch.setattr(ops, "_CONV_KMAJOR", knob)
         on = 1 if knob else 0
@@ -477,27 +530,33 @@ def test_conv_k_order_follows_the_tile_plan(monkeypatch):
         # the split-K rule: the 16x16 level at UNet batch 12 (every Cin of that level), not at batch 24 (128 tiles: un-split 128x128 plan) or batch 4
         sk = 1 if knob == 2 else 0
         for cin in (640, 1280, 1920, 2560):
-            assert ops._tile_label(12 * 16 * 16, 1280, True, 9 * cin, False, True) == "192x320,splitK", cin
+            assert ops.plan_label(ops.conv_plan(12, 16, 16, cin, 1280)) == "192x320,splitK", cin
             assert ops.conv_k_order(12 * 16 * 16, cin, 1280) == sk, (knob, cin)
         assert ops.conv_k_order(12 * 16 * 16, 1280, 1280, stride=2) == sk               # (a stride-2 launch of that grid takes the same plan; its slab form is refused by the launcher, not here)
         assert ops.conv_k_order(4 * 16 * 16, 1280, 1280) == 0
         # the slab form of the loop needs every split-K block's K range to start at a chunk boundary (launcher: ceil(KT / split) % 9 == 0): the two
         # frequent convs of the level (Cin 1280: 6 launches per evaluation, 2560: 2) qualify, Cin 640 / 1920 (one launch each) run the tap form
         for cin, slab in ((640, False), (1280, True), (1920, False), (2560, True)):
-            sp = ops._conv_t320_split(12 * 16 * 16, 1280, 9 * cin)
+            sp = t320_split(12, 16, cin, 1280)
             kt = 9 * cin // 64
             assert sp == 4 and ((-(-kt // sp)) % 9 == 0) == slab, (cin, sp)
+            assert (ops.conv_plan(12, 16, 16, cin, 1280, k_order=1).WA == 4) == slab, cin     # ... and the launcher agrees (WA = 4: the slab form)
     # round 5: the split plan also takes the 32x32-level convs with >= 180 K tiles (AE_CONV_T320_SPLITK default 3), in the chunk-major order; not the shorter ones
     monkeypatch.setattr(ops, "_CONV_KMAJOR", 2)
-    monkeypatch.delenv("AE_CONV_T320_SPLITK", raising=False)
-    assert ops._conv_t320_split(12 * 32 * 32, 640, 9 * 1920) == 2 and ops._conv_t320_split(12 * 32 * 32, 640, 9 * 1280) == 2
+    assert t320_split(12, 32, 1920, 640) == 2 and t320_split(12, 32, 1280, 640) == 2
     assert ops.conv_k_order(12 * 32 * 32, 1920, 640) == 1 and ops.conv_k_order(12 * 32 * 32, 1280, 640) == 1
-    assert ops._conv_t320_split(12 * 32 * 32, 640, 9 * 960) == 0 and ops.conv_k_order(12 * 32 * 32, 960, 640) == 0 and ops.conv_k_order(12 * 32 * 32, 640, 640) == 0
-    monkeypatch.setenv("AE_CONV_T320_SPLITK", "2")
-    assert ops._conv_t320_split(12 * 32 * 32, 640, 9 * 1920) == 0 and ops.conv_k_order(12 * 32 * 32, 1920, 640) == 0
-    monkeypatch.delenv("AE_CONV_T320_SPLITK", raising=False)
-    monkeypatch.setenv("AE_GEMM_GLDS", "0")
-    assert ops.conv_k_order(12 * 64 * 64, 320, 320) == 0                               # the chunk-major order exists in the LDS-DMA loader only
+    assert t320_split(12, 32, 960, 640) == 0 and ops.conv_k_order(12 * 32 * 32, 960, 640) == 0 and ops.conv_k_order(12 * 32 * 32, 640, 640) == 0
+    # the library latches its knobs when it first plans: a non-default value is asked of a fresh process (host only, no GPU)
+    child = ("import json; from anyedit_amd import ops; p = ops.conv_plan(12, 32, 32, 1920, 640); "
+             "print(json.dumps(dict(label=ops.plan_label(p), split=p.splitk, k1920=ops.conv_k_order(12 * 32 * 32, 1920, 640), k320=ops.conv_k_order(12 * 64 * 64, 320, 320))))")
+
+    def ask(**env):
+        r = subprocess.run([sys.executable, "-c", child], cwd=ROOT, env=dict(os.environ, AE_CONV_KMAJOR="2", **env), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads(r.stdout.strip().splitlines()[-1])
+    a = ask(AE_CONV_T320_SPLITK="2")
+    assert (a["label"], a["split"]) == ("128x128", 1) and a["k1920"] == 0 and a["k320"] == 1   # 0 = not the 192x320 split plan: its grids end at 64 tiles
+    assert ask(AE_GEMM_GLDS="0")["k320"] == 0                                      # the chunk-major order exists in the LDS-DMA loader only
 
 
 def test_upsample_conv_as_four_2x2_convs_identity():

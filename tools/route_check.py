@@ -2,9 +2,10 @@
 
 For each case of tests/route_cases.py (one process, run with no AE_* routing variable set; tests/test_kernel_routes.py starts it that way):
   1. seeded bf16 operands; the op runs through `ops` once under torch.profiler (device activity) -> the kernel names of that case;
-  2. the case must reach every instantiation whose `default` ledger row lists it, and the Python mirrors of the plan must agree with what ran
-     (`ops._tile_label`: tile shape / three-stage ring; `ops._conv_splitk`: a split plan <=> the split-K reduce ran, and the factor equals the
-     library's own plan, `ae_conv3x3_workspace_floats`);
+  2. the case must reach every instantiation whose `default` ledger row lists it, and the library's own report of its plan (`ops.conv_plan` /
+     `ops.up2_plan` / `ops.gemm_plan`: the launch selection run without launching) must name what ran: all twelve template arguments of the
+     gemm_kernel, a split plan <=> the split-K reduce ran (the factor equal to what `ae_conv3x3_workspace_floats` sizes), the stand-alone
+     column-statistics kernel <=> the report says so;
   3. every output (and column / row statistics buffer) is a view of a larger allocation whose guard areas — rows before and after, columns past
      N where the op takes a row stride, slabs past ceil(M / 32) — hold a sentinel bit pattern that must be unchanged after the launch;
   4. a second run (fresh guarded buffers) must be bit-identical;
@@ -259,12 +260,9 @@ def run_conv(c, ops, gen):
         ref += res.to(F64)[rows]
     absprod = P.abs() @ Wt.abs().t()
     bnd = (2.0 ** -20 if f32 else 2.0 ** -8) * ref.abs() + A_ACC * absprod + 1e-30
-    label = ops._tile_label(M, Cout, True, 9 * ((Cin + 63) // 64 * 64), False, Cin % 64 == 0)
-    split_py = ops._conv_splitk(M, Cout, 9 * ((Cin + 63) // 64 * 64))
     nws = ops.lib.ae_conv3x3_workspace_floats(B, H, W, Cin, Cout, s, int(ups))
-    split_c = nws // (M * Cout) if nws else 1
-    return dict(launch=launch, rows=rows, ref=ref, bnd=bnd, cs=cs, M=M, N=Cout, conv=True, label=label,
-                split=(split_py, split_c), f32=f32)
+    return dict(launch=launch, rows=rows, ref=ref, bnd=bnd, cs=cs, M=M, N=Cout, conv=True, f32=f32,
+                plan=lambda: ops.conv_plan(B, H, W, Cin, Cout, s, ups, f32, cs, k), ws_split=nws // (M * Cout) if nws else 1)
 
 
 def _stats_with_tail(S, N, tail=4):
@@ -314,7 +312,8 @@ def run_up2(c, ops, gen):
         ref[sel] += P @ Wt.t()
         absprod[sel] = P.abs() @ Wt.abs().t()
     bnd = 2.0 ** -8 * ref.abs() + A_ACC * absprod + 1e-30
-    return dict(launch=launch, rows=rows, ref=ref, bnd=bnd, cs=cs, M=M, N=Cout, conv=True, label=None, split=None, f32=False, sample_rows=Ho * Wo)
+    return dict(launch=launch, rows=rows, ref=ref, bnd=bnd, cs=cs, M=M, N=Cout, conv=True, f32=False, sample_rows=Ho * Wo,
+                plan=lambda: ops.up2_plan(B, H, W, Cin, Cout, cs))
 
 
 def run_gemm(c, ops, gen, ln=False):
@@ -379,9 +378,8 @@ def run_gemm(c, ops, gen, ln=False):
     if res is not None:
         ref = ref + res.to(F64)[rows]
     bnd = (2.0 ** -20 if f32 else 2.0 ** -8) * ref.abs() + acc + 1e-30
-    dma_ok = K % 64 == 0 and (a2k is None or a2k % 64 == 0)
-    label = ops._tile_label(M, N, False, K, epi == ops.EPI_GEGLU, dma_ok, xe2=ln)
-    return dict(launch=launch, rows=rows, ref=ref, bnd=bnd, cs=cs, rs=rs, M=M, N=n_out, conv=False, label=label, split=None, f32=f32)
+    return dict(launch=launch, rows=rows, ref=ref, bnd=bnd, cs=cs, rs=rs, M=M, N=n_out, conv=False, f32=f32,
+                plan=lambda: ops.gemm_plan(M, N, K, epi, a2k or 0, f32, cs, 2 if ln else 1 if rs else 0))
 
 
 def run_attn(c, ops, gen):
@@ -494,31 +492,32 @@ def run_attn(c, ops, gen):
         return torch.cat([lv[bb, hh, qsel] for bb, hh in pairs])[:, None]
 
     lse = [dict(name=n, ref=torch.cat(lrefs[i])[:, None], bnd=torch.cat(lbnds[i])[:, None]) for i, n in enumerate(("lse", "lse2")[:2 if nk2 else 1])]
-    return dict(launch=launch, ref=torch.cat(refs), bnd=torch.cat(bnds), gather=gather, cs=False, conv=False, label=None, split=None, f32=False,
+    return dict(launch=launch, ref=torch.cat(refs), bnd=torch.cat(bnds), gather=gather, cs=False, conv=False, f32=False,
                 lse=lse, gather_lse=gather_lse)
 
 
-# --------------------------------------------------------------------------------------------------- mirrors
-def mirror_check(spec, keys):
-    """ops._tile_label / ops._conv_splitk against the kernels that ran (the main gemm_kernel's BM x BN and ring depth; split <=> reduce)"""
-    gk = [k for k in keys if k.startswith("gemm_kernel<")]
-    if not gk or (spec["label"] is None and spec["split"] is None):
+# --------------------------------------------------------------------------------------------------- the library's report of its plan
+def plan_check(spec, keys):
+    """the library's report of the launch (spec["plan"]) against the kernels that ran: the full gemm_kernel key, the split-K reduce, the split
+    factor, the stand-alone column-statistics kernel"""
+    if "plan" not in spec:
         return "n/a"
-    a = [x.strip() for x in gk[0][len("gemm_kernel<"):-1].split(",")]
-    seen = f"{a[0]}x{a[1]}" + (",ring3" if a[7] == "3" else "")
+    p = spec["plan"]()
+    if p is None:
+        raise CaseFailure("the plan query refuses a launch that ran")
+    b = ("false", "true")
+    want = [] if p.rowpanel else [f"gemm_kernel<{p.BM}, {p.BN}, {p.AMODE}, {p.WAVES_M}, {p.WAVES_N}, {b[p.GLDS]}, {p.WAVES_K}, {p.STAGES}, {b[p.CS]}, {p.LAB}, {p.WA}, {p.XE}>"]
+    ran = sorted(set(k for k in keys if k.startswith("gemm_kernel<")))
     problems = []
-    if spec["label"] is not None:
-        lab = spec["label"]
-        want = lab.replace(",splitK", "")
-        if want != seen:
-            problems.append(f"_tile_label says {lab}, {seen} ran")
-    if spec["split"] is not None:
-        s_py, s_c = spec["split"]
-        reduced = "splitk_reduce_kernel" in keys
-        if s_py != s_c:
-            problems.append(f"_conv_splitk says {s_py}, the library plans {s_c}")
-        if (s_c > 1) != reduced:
-            problems.append(f"plan split {s_c} but split-K reduce {'ran' if reduced else 'did not run'}")
+    if ran != want:
+        problems.append(f"the plan says {want}, {ran} ran")
+    reduced, stats = "splitk_reduce_kernel" in keys, "colstats_kernel" in keys
+    if (p.splitk > 1) != reduced or bool(p.reduce) != reduced:
+        problems.append(f"plan split {p.splitk} (reduce {p.reduce}) but split-K reduce {'ran' if reduced else 'did not run'}")
+    if p.splitk != spec.get("ws_split", 1):
+        problems.append(f"the plan splits {p.splitk} ways, the workspace is sized for {spec.get('ws_split', 1)}")
+    if bool(p.colstats) != stats:
+        problems.append(f"plan colstats {p.colstats} but the stand-alone colstats_kernel {'ran' if stats else 'did not run'}")
     if problems:
         raise CaseFailure("; ".join(problems))
     return "ok"
@@ -533,7 +532,7 @@ def run_case(c, ops):
     (o1, st1, *ex1), names = profiled(spec["launch"])
     ex1 = ex1[0] if ex1 else []          # attention: the guarded log-sum-exp buffers
     names, keys = route_keys(names)
-    res = dict(id=c["id"], kernels=names, keys=sorted(set(keys)), ok=False, ratio=None, guards=None, mirror=None, error=None)
+    res = dict(id=c["id"], kernels=names, keys=sorted(set(keys)), ok=False, ratio=None, guards=None, plan=None, error=None)
     if "lse" in spec:
         res["lse_ratio"] = None
     try:
@@ -541,7 +540,7 @@ def run_case(c, ops):
         missing = [k for k in want if k not in keys]
         if missing:
             raise CaseFailure(f"declared instantiation(s) not reached: {missing}")
-        res["mirror"] = mirror_check(spec, keys)
+        res["plan"] = plan_check(spec, keys)
         o2, st2, *ex2 = spec["launch"]()
         ex2 = ex2[0] if ex2 else []
         torch.cuda.synchronize()
@@ -609,7 +608,7 @@ def main():
         rt = f"{r['ratio']:.3f}" if r["ratio"] is not None else "-"
         if "lse_ratio" in r:
             rt += " lse_ratio " + (f"{r['lse_ratio']:.3f}" if r["lse_ratio"] is not None else "-")
-        print(f"{'PASS' if r['ok'] else 'FAIL'} {r['id']:24s} {time.time() - t1:5.1f}s ratio {rt:>6s} guards {r['guards']} mirror {r['mirror']} "
+        print(f"{'PASS' if r['ok'] else 'FAIL'} {r['id']:24s} {time.time() - t1:5.1f}s ratio {rt:>6s} guards {r['guards']} plan {r['plan']} "
               f"kernels {r['keys'] or r['kernels']}" + (f"  ERROR {r['error']}" if r["error"] else ""), flush=True)
     summary = dict(results=results, aborted=aborted, seconds=round(time.time() - t0, 1))
     print("ROUTE_SUMMARY " + json.dumps(summary), flush=True)
