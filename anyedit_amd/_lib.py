@@ -145,6 +145,10 @@ SIGNATURES = {
     "ae_gdino_neck_groupnorm_workspace_floats": [c_int, c_int],
     "ae_gdino_neck_groupnorm": [c_void_p, c_long, c_void_p, c_void_p, c_float, c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_void_p],
     "ae_gdino_ground": [c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "ae_hed_stem_bf16": [c_void_p, c_int, c_long, c_long, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "ae_relu_bf16": [c_void_p, c_long, c_void_p],
+    "ae_hed_tail_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "ae_hed_fuse": [c_void_p] * 7 + [c_int] * 4 + [c_void_p],
 }
 _RESTYPES = {"ae_last_error": ctypes.c_char_p, "ae_groupnorm_workspace_floats": c_long, "ae_conv3x3_workspace_floats": c_long,
              "ae_groupnorm_bwd_workspace_floats": c_long, "ae_attn_fp8_workspace_bytes": c_long, "ae_attn_bwd_workspace_floats": c_long,

@@ -400,6 +400,26 @@ def load_groundingdino(model, path_or_state_dict, location="cpu"):
     return layout
 
 
+HED_PREFIXES = ("module.", "netNetwork.")
+
+
+def load_hed(model, path_or_state_dict, location="cpu"):
+    """Fills a `hed.ControlNetHED_Apache2` (HED/__init__.py:57 `load_state_dict(torch.load(path))`) from a `ControlNetHED.pth` file or a state
+    dict: `norm`, `blockN.convs.M.{weight,bias}`, `blockN.projection.{weight,bias}`, bare or with a `module.` or `netNetwork.` prefix on every
+    key.  Strict: missing or unexpected keys are reported as `load_state_dict(strict=True)` reports them.  Returns the form found."""
+    sd = path_or_state_dict
+    if not isinstance(sd, dict):
+        from anyedit_amd.cldm.model import load_state_dict
+        sd = load_state_dict(sd, location)
+    layout = "state_dict"
+    for pref in HED_PREFIXES:
+        if sd and all(k.startswith(pref) for k in sd):
+            sd, layout = {k[len(pref):]: v for k, v in sd.items()}, pref.rstrip(".")
+            break
+    model.load_state_dict(sd, strict=True)
+    return layout
+
+
 def load_sd_checkpoint(path, unet=None, vae=None, text_encoder=None, location="cpu"):
     """`load_unet_weights`' sibling for a FULL SD-1.5 state dict (CompVis lineage): routes `model.diffusion_model.*` to `unet`,
     `first_stage_model.*` to `vae` and `cond_stage_model.*` to `text_encoder` (a FrozenCLIPEmbedder); a part given as None is skipped.

@@ -1486,6 +1486,110 @@ def gdino_ground(pred_logits, pred_boxes, box_threshold, text_threshold, out=Non
     return out
 
 
+# --------------------------------------------------------------------------- HED edge detector (csrc/hed.hip)
+HED_STEM_CMAX = 512
+HED_LEVELS = 5
+HED_MIN_SIDE = 1 << (HED_LEVELS - 1)      # below it the fifth side map is empty
+HED_MAX_SIDE = 16384
+
+
+def _out_buf(out, dtype, shape, name, device):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    return _target(out, dtype, shape, name)
+
+
+def hed_stem(x, norm, w, bias, out=None):
+    """relu(conv3x3(x - norm, w) + bias) -> bf16 channels-last rows [B*H*W, C1], in one launch.  x: a uint8 image batch [B, H, W, 3] or fp32
+    [B, 3, H, W] (any strides: the kernel addresses it by element strides); norm fp32 of 3 values, w fp32 [C1, 3, 3, 3], bias fp32 [C1], C1 % 8
+    == 0 and at most 512.  The zero padding applies to x - norm.  Returns (rows, B, H, W)."""
+    if not x.is_cuda:
+        raise ValueError("hed_stem.x: expected a GPU tensor (anyedit_amd has no CPU path)")
+    if x.dim() != 4:
+        raise ValueError(f"hed_stem: x must be uint8 [B, H, W, 3] or fp32 [B, 3, H, W], got shape {tuple(x.shape)}")
+    if x.dtype == torch.uint8:
+        B, H, W, C = x.shape
+        sb, sh, sw, sc = x.stride()
+    elif x.dtype == torch.float32:
+        B, C, H, W = x.shape
+        sb, sc, sh, sw = x.stride()
+    else:
+        raise TypeError(f"hed_stem.x: expected torch.uint8 [B, H, W, 3] or torch.float32 [B, 3, H, W], got {x.dtype}")
+    if C != 3 or B < 1 or H < 1 or W < 1:
+        raise ValueError(f"hed_stem: x must be uint8 [B, H, W, 3] or fp32 [B, 3, H, W], got shape {tuple(x.shape)}")
+    norm = _dense(norm, torch.float32, "hed_stem.norm")
+    w = _dense(w, torch.float32, "hed_stem.w", 4)
+    bias = _dense(bias, torch.float32, "hed_stem.bias", 1)
+    C1 = w.shape[0]
+    if tuple(w.shape) != (C1, 3, 3, 3) or norm.numel() != 3 or bias.numel() != C1:
+        raise ValueError(f"hed_stem: need w [C1, 3, 3, 3], norm of 3 values and bias [C1], got {tuple(w.shape)}, {tuple(norm.shape)}, {tuple(bias.shape)}")
+    out = _out_buf(out, BF16, (B * H * W, C1), "hed_stem.out", x.device)
+    check(lib.ae_hed_stem_bf16(_p(x), 1 if x.dtype == torch.float32 else 0, sb, sc, sh, sw, _p(norm), _p(w), _p(bias), _p(out), B, H, W, C1, _s()),
+          "ae_hed_stem_bf16")
+    return out, B, H, W
+
+
+def relu_(x):
+    """ReLU in place on a contiguous bf16 tensor; returns it."""
+    _chk(x, BF16, "relu_.x")
+    if not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("relu_: x must be a contiguous, non-empty tensor (the kernel writes it in place)")
+    check(lib.ae_relu_bf16(_p(x), x.numel(), _s()), "ae_relu_bf16")
+    return x
+
+
+def hed_tail(y, wp, bp, B, H, W, pool=True, proj=None, pooled=None):
+    """The end of a HED block on its last convolution's output y BEFORE the ReLU (bf16 rows [B*H*W, C], C % 8 == 0), in one pass:
+    proj fp32 [B, H, W] = sum_c relu(y)[c] * wp[c] + bp (fp32 weights wp [C], bp of one value, fp32 accumulation) and, with `pool`, pooled bf16
+    rows [B*(H//2)*(W//2), C] = max_pool2d(relu(y), 2, 2).  Returns (proj, pooled or None)."""
+    _chk(y, BF16, "hed_tail.y", 2)
+    C = y.shape[1]
+    if y.shape[0] != B * H * W or not y.is_contiguous() or B < 1 or H < 1 or W < 1:
+        raise ValueError(f"hed_tail: y must be contiguous [B*H*W, C] = [{B * H * W}, C], got {tuple(y.shape)}")
+    wp = _dense(wp, torch.float32, "hed_tail.wp").reshape(-1)
+    bp = _dense(bp, torch.float32, "hed_tail.bp").reshape(-1)
+    if wp.numel() != C or bp.numel() != 1:
+        raise ValueError(f"hed_tail: need {C} projection weights and one bias, got {wp.numel()} and {bp.numel()}")
+    proj = _out_buf(proj, torch.float32, (B, H, W), "hed_tail.proj", y.device)
+    if pool:
+        if H < 2 or W < 2:
+            raise ValueError(f"hed_tail: a {H} x {W} map has no 2x2 window to pool")
+        pooled = _out_buf(pooled, BF16, (B * (H // 2) * (W // 2), C), "hed_tail.pooled", y.device)
+    elif pooled is not None:
+        raise ValueError("hed_tail: a pooled buffer was given with pool=False")
+    check(lib.ae_hed_tail_bf16(_p(y), _p(wp), _p(bp), _p(proj), _p(pooled), B, H, W, C, _s()), "ae_hed_tail_bf16")
+    return proj, pooled
+
+
+def hed_fuse(sides, invert=True, out=None, logits=None, want_logits=False):
+    """HEDdetector's arithmetic after the network: the five fp32 side maps [B, H >> k, W >> k] (or [B, 1, h, w]) resized to H x W (bilinear,
+    half-pixel centres, edge clamp), averaged, sigmoid, * 255, clip, truncated to uint8 [B, H, W]; `invert`: 255 - v.  With `want_logits` (or a
+    `logits` buffer) the fp32 mean before the sigmoid is written too.  Returns the uint8 map, or (map, logits)."""
+    if len(sides) != HED_LEVELS:
+        raise ValueError(f"hed_fuse: expected {HED_LEVELS} side maps, got {len(sides)}")
+    s0 = sides[0]
+    _chk(s0, torch.float32, "hed_fuse.sides[0]")
+    if s0.dim() == 4 and s0.shape[1] == 1:
+        sides = [s.squeeze(1) if s.dim() == 4 else s for s in sides]
+        s0 = sides[0]
+    if s0.dim() != 3:
+        raise ValueError(f"hed_fuse: side maps must be [B, h, w] or [B, 1, h, w], got {tuple(s0.shape)}")
+    B, H, W = s0.shape
+    if not (HED_MIN_SIDE <= H <= HED_MAX_SIDE and HED_MIN_SIDE <= W <= HED_MAX_SIDE):
+        raise ValueError(f"hed_fuse: sides of {HED_MIN_SIDE} .. {HED_MAX_SIDE} pixels are covered, got {H} x {W}")
+    dense = []
+    for k, s in enumerate(sides):
+        _chk(s, torch.float32, f"hed_fuse.sides[{k}]", 3)
+        if tuple(s.shape) != (B, H >> k, W >> k):
+            raise ValueError(f"hed_fuse: side map {k} must be [{B}, {H >> k}, {W >> k}], got {tuple(s.shape)}")
+        dense.append(_tmp(s.contiguous()))
+    out = _out_buf(out, torch.uint8, (B, H, W), "hed_fuse.out", s0.device)
+    if want_logits or logits is not None:
+        logits = _out_buf(logits, torch.float32, (B, H, W), "hed_fuse.logits", s0.device)
+    check(lib.ae_hed_fuse(*[_p(s) for s in dense], _p(out), _p(logits), B, H, W, 1 if invert else 0, _s()), "ae_hed_fuse")
+    return out if logits is None else (out, logits)
+
+
 def rows_to_nchw_out(x, out):
     """channels-last bf16 rows [B*H*W, C] contiguous -> the given [B, C, H, W] buffer (fp32 or bf16, contiguous): `rows_to_nchw` into a
     buffer the caller owns (no allocation)."""
@@ -2370,3 +2474,13 @@ expert_kv_dgrad = _wrap_profiled(expert_kv_dgrad, lambda _r, dy, W, experts, tok
     f"expert_kv_dgrad_kernel|rows={dy.shape[0]} N={W.shape[1]} Dc={W.shape[2]}", 2.0 * dy.shape[0] * W.shape[1] * W.shape[2], 4.0 * (dy.shape[0] // tokens) * W.shape[1] * W.shape[2]))
 expert_kv_wgrad = _wrap_profiled(expert_kv_wgrad, lambda _r, dy, x, experts, tokens, n_experts, out=None: (
     f"expert_kv_wgrad_kernel|rows={dy.shape[0]} N={dy.shape[1]} Dc={x.shape[1]} E={n_experts}", 2.0 * dy.shape[0] * dy.shape[1] * x.shape[1], 4.0 * n_experts * dy.shape[1] * x.shape[1]))
+hed_stem = _wrap_profiled(hed_stem, lambda _r, x, norm, w, bias, out=None: (
+    f"hed_stem_kernel<{'u8' if x.dtype == torch.uint8 else 'f32'}>|M={_r[0].shape[0]} C1={_r[0].shape[1]}", 2.0 * 27 * _r[0].numel(),
+    float(x.numel() * x.element_size() + 2 * _r[0].numel())))
+relu_ = _wrap_profiled(relu_, lambda _r, x: (f"relu_bf16_kernel|n={x.numel()}", 0.0, 4.0 * x.numel()))
+hed_tail = _wrap_profiled(hed_tail, lambda _r, y, wp, bp, B, H, W, pool=True, proj=None, pooled=None: (
+    f"hed_tail_kernel<{'pool' if pool else 'last'}>|M={y.shape[0]} C={y.shape[1]}", 2.0 * y.numel(),
+    float(2 * y.numel() + 4 * _r[0].numel() + (2 * _r[1].numel() if pool else 0))))
+hed_fuse = _wrap_profiled(hed_fuse, lambda _r, sides, invert=True, out=None, logits=None, want_logits=False: (
+    f"hed_fuse_kernel|B={sides[0].shape[0]} {sides[0].shape[-2]}x{sides[0].shape[-1]}", 0.0,
+    float(4 * sum(s.numel() for s in sides) + sides[0].numel() * (1 + 4 * (want_logits or logits is not None)))))

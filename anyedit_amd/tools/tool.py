@@ -52,6 +52,13 @@ def select_target_boxes(boxes, pred_phrases, target_object):
     return torch.stack([b for b, _ in picked]), torch.tensor([s for _, s in picked])
 
 
+def img2scribble(image_path, output_path, hed_model):
+    """The `visual_scribble` branch of visual_condition_tool.py (:263-264): `hed_model(image_path, visual_path)` with `hed_model` an
+    `anyedit_amd.hed.HEDdetector` — the inverted HED edge map of the image file, written to `output_path`.  Returns `output_path`."""
+    hed_model(image_path, output_path)
+    return output_path
+
+
 def maskgeneration(det_model, sam_model, image_path, det_prompt, mask_mode='max', box_threshold=0.25, text_threshold=0.25,
                    target_object=None, device="cuda"):
     """tool.py:166-269.  Returns (mask_pil, image_pil, mask_bbox_pil, union_region); (None, image_pil, None, None) when no box or an

@@ -625,6 +625,30 @@ int ae_gdino_neck_groupnorm(const float* x, long ldx, const float* gamma, const 
 int ae_gdino_ground(const float* pred_logits, const float* pred_boxes, float box_threshold, float text_threshold, int* count, int* indices, float* scores,
                     float* boxes, void* token_bits, int B, int nq, int T, void* stream);
 
+/* ---- HED edge detector (csrc/hed.hip; AnyEdit_Collection/other_modules/HED/__init__.py): what stands around the 3x3 convolutions, which are
+ * ae_conv3x3_bf16.  Bandwidth-bound kernels, no atomics, fixed summation orders: every launch is deterministic; current stream only, no host
+ * synchronisation, no allocation.
+ * ae_hed_stem_bf16: `h = x - self.norm` (:45) and block1.convs[0] with its ReLU (:19, :29-30) in one launch.  x: uint8 (x_is_f32 = 0) or fp32 (1),
+ *   element (b, c, y, x) at b sb + c sc + y sh + x sw (elements): a uint8 image [B, H, W, 3] and the fp32 [B, 3, H, W] of __call__ alike.  norm
+ *   fp32 [3], w fp32 [C1, 3, 3, 3], bias fp32 [C1]; fp32 accumulation starting from the bias, taps in the order of w.  The zero padding applies
+ *   to x - norm: a tap outside the image contributes 0.  out bf16 [B*H*W, C1], C1 % 8 == 0, C1 <= 512.
+ * ae_relu_bf16: x = max(x, 0) in place on n bf16 values (:30 for the convolutions that are not last in their block); negative values, -0 and
+ *   negative NaNs become +0.
+ * ae_hed_tail_bf16: the end of DoubleConvBlock.__call__ (:30-31) and the next block's max_pool2d (:27) in one pass.  y bf16 [B, H, W, C], the
+ *   last convolution's output BEFORE its ReLU, C % 8 == 0; wp fp32 [C], bp fp32 [1] (on the device).  proj fp32 [B, H, W] = sum_c relu(y)[c] wp[c]
+ *   + bp, fp32 accumulation.  pooled bf16 [B, H/2, W/2, C] = max_pool2d(relu(y), 2, 2) (floor division: an odd last row or column is projected,
+ *   not pooled), or NULL (block 5).  relu(y) itself is never written.
+ * ae_hed_fuse: HEDdetector.__call__ :67-73.  p0 .. p4 fp32 [B, H >> k, W >> k], 16 <= H, W <= 16384.  Each is resized to H x W as
+ *   cv2.resize(INTER_LINEAR) / F.interpolate(mode="bilinear", align_corners=False) define it (half-pixel centres, edge clamp, scale = src / dst per
+ *   axis), the five are averaged in fp32, then sigmoid in fp64, * 255, clip, truncation.  out uint8 [B, H, W] (invert: 255 - v, cv2.bitwise_not);
+ *   logits: optional fp32 [B, H, W], the mean before the sigmoid.                                                                             */
+int ae_hed_stem_bf16(const void* x, int x_is_f32, long sb, long sc, long sh, long sw, const float* norm, const float* w, const float* bias, void* out,
+                     int B, int H, int W, int C1, void* stream);
+int ae_relu_bf16(void* x, long n, void* stream);
+int ae_hed_tail_bf16(const void* y, const float* wp, const float* bp, float* proj, void* pooled, int B, int H, int W, int C, void* stream);
+int ae_hed_fuse(const float* p0, const float* p1, const float* p2, const float* p3, const float* p4, void* out, float* logits, int B, int H, int W,
+                int invert, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
