@@ -149,6 +149,12 @@ SIGNATURES = {
     "ae_relu_bf16": [c_void_p, c_long, c_void_p],
     "ae_hed_tail_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "ae_hed_fuse": [c_void_p] * 7 + [c_int] * 4 + [c_void_p],
+    "ae_dpt_reassemble_bf16": [c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "ae_dpt_resize_bf16": [c_void_p] * 4 + [c_int] * 6 + [c_void_p],
+    "ae_dpt_relu_bf16": [c_void_p, c_void_p, c_long, c_void_p],
+    "ae_dpt_tail_bf16": [c_void_p] * 4 + [c_int] * 4 + [c_void_p],
+    "ae_depth_resize_minmax_f32": [c_void_p] * 3 + [c_int] * 5 + [c_void_p],
+    "ae_depth_colorize_u8": [c_void_p] * 4 + [c_int] * 3 + [c_void_p],
 }
 _RESTYPES = {"ae_last_error": ctypes.c_char_p, "ae_groupnorm_workspace_floats": c_long, "ae_conv3x3_workspace_floats": c_long,
              "ae_groupnorm_bwd_workspace_floats": c_long, "ae_attn_fp8_workspace_bytes": c_long, "ae_attn_bwd_workspace_floats": c_long,

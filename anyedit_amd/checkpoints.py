@@ -420,6 +420,21 @@ def load_hed(model, path_or_state_dict, location="cpu"):
     return layout
 
 
+def load_depth_anything(model, path_or_state_dict, location="cpu"):
+    """Fills a `depth_anything_v2.DepthAnythingV2` from a `depth_anything_v2_vit{s,b,l}.pth` file or a state dict: `pretrained.*` (the DINOv2 tower)
+    and `depth_head.*`, bare or with a `module.` prefix on every key.  Strict: missing or unexpected keys are reported as
+    `load_state_dict(strict=True)` reports them.  Returns the form found."""
+    sd = path_or_state_dict
+    if not isinstance(sd, dict):
+        from anyedit_amd.cldm.model import load_state_dict
+        sd = load_state_dict(sd, location)
+    layout = "state_dict"
+    if sd and all(k.startswith("module.") for k in sd):
+        sd, layout = {k[len("module."):]: v for k, v in sd.items()}, "module"
+    model.load_state_dict(sd, strict=True)
+    return layout
+
+
 def load_sd_checkpoint(path, unet=None, vae=None, text_encoder=None, location="cpu"):
     """`load_unet_weights`' sibling for a FULL SD-1.5 state dict (CompVis lineage): routes `model.diffusion_model.*` to `unet`,
     `first_stage_model.*` to `vae` and `cond_stage_model.*` to `text_encoder` (a FrozenCLIPEmbedder); a part given as None is skipped.

@@ -1590,6 +1590,126 @@ def hed_fuse(sides, invert=True, out=None, logits=None, want_logits=False):
     return out if logits is None else (out, logits)
 
 
+# --------------------------------------------------------------------------- Depth Anything V2's DPT head (csrc/dpt.hip)
+DPT_MAX_SIDE = 16384
+DPT_STRIDES = (1, 2, 4)
+
+
+def _rows(t, name, rows, C=None):
+    """a contiguous bf16 row buffer [rows, C] with C % 8 == 0"""
+    _chk(t, BF16, name, 2)
+    if t.shape[0] != rows or not t.is_contiguous() or (C is not None and t.shape[1] != C):
+        raise ValueError(f"{name}: expected contiguous rows [{rows}, {'C' if C is None else C}], got {tuple(t.shape)} strides {t.stride()}")
+    if t.shape[1] % 8 or t.shape[1] < 8:
+        raise ValueError(f"{name}: {t.shape[1]} channels: the kernel takes 8 channels (16 bytes) per lane, C must be a multiple of 8")
+    return t
+
+
+def _sides(what, *sides):
+    if any(s < 1 or s > DPT_MAX_SIDE for s in sides):
+        raise ValueError(f"{what}: sides of 1 .. {DPT_MAX_SIDE} are covered, got {sides}")
+
+
+def dpt_reassemble(prod, bias, B, gh, gw, k, out=None):
+    """The data movement of DPTHead's `projects[i]` + `resize_layers[i]` after their products.  prod: fp32 [B * (1 + gh gw), k k oc] (row stride free,
+    a multiple of 4), one row per token with each image's class row first, columns (ky k + kx) oc + c; bias fp32 [oc].  Returns bf16 rows
+    [B * (gh k) * (gw k), oc] = bf16(prod + bias) at pixel (gy k + ky, gx k + kx); the class rows are skipped.  k in {1, 2, 4}."""
+    _chk(prod, torch.float32, "dpt_reassemble.prod", 2)
+    if k not in DPT_STRIDES:
+        raise ValueError(f"dpt_reassemble: k={k} is not covered (the head's resize layers have strides {DPT_STRIDES})")
+    if B < 1 or gh < 1 or gw < 1:
+        raise ValueError(f"dpt_reassemble: bad sizes B={B} grid {gh}x{gw}")
+    _sides("dpt_reassemble", gh * k, gw * k)
+    bias = _dense(bias, torch.float32, "dpt_reassemble.bias", 1)
+    oc = bias.numel()
+    if oc % 8 or oc < 8:
+        raise ValueError(f"dpt_reassemble: oc={oc} must be a multiple of 8 (16 bytes per lane)")
+    if tuple(prod.shape) != (B * (1 + gh * gw), k * k * oc) or prod.stride(1) != 1 or prod.stride(0) % 4 or prod.stride(0) < k * k * oc:
+        raise ValueError(f"dpt_reassemble: prod must be [B * (1 + gh gw), k k oc] = [{B * (1 + gh * gw)}, {k * k * oc}] with unit inner stride and a row "
+                         f"stride that is a multiple of 4, got {tuple(prod.shape)} strides {prod.stride()}")
+    out = _out_buf(out, BF16, (B * gh * k * gw * k, oc), "dpt_reassemble.out", prod.device)
+    check(lib.ae_dpt_reassemble_bf16(_p(prod), prod.stride(0), _p(bias), _p(out), B, gh, gw, k, oc, _s()), "ae_dpt_reassemble_bf16")
+    return out
+
+
+def dpt_resize(x, B, h, w, H, W, addend=None, out=None, relu_out=None, want_relu=False):
+    """F.interpolate(mode="bilinear", align_corners=True) on channels-last bf16 rows: x [B*h*w, C] -> [B*H*W, C], any two sizes (a side of 1
+    included), + `addend` ([B*H*W, C] bf16) in fp32 before the single rounding.  With `want_relu` (or a `relu_out` buffer) relu(result) is written
+    too.  Returns the rows, or (rows, relu rows)."""
+    if B < 1:
+        raise ValueError(f"dpt_resize: bad batch {B}")
+    _sides("dpt_resize", h, w, H, W)
+    _rows(x, "dpt_resize.x", B * h * w)
+    C = x.shape[1]
+    if addend is not None:
+        _rows(addend, "dpt_resize.addend", B * H * W, C)
+    out = _out_buf(out, BF16, (B * H * W, C), "dpt_resize.out", x.device)
+    if want_relu or relu_out is not None:
+        relu_out = _out_buf(relu_out, BF16, (B * H * W, C), "dpt_resize.relu_out", x.device)
+    check(lib.ae_dpt_resize_bf16(_p(x), _p(addend), _p(out), _p(relu_out), B, h, w, H, W, C, _s()), "ae_dpt_resize_bf16")
+    return out if relu_out is None else (out, relu_out)
+
+
+def dpt_relu(x, out=None):
+    """relu(x) out of place on contiguous bf16 rows [rows, C], C % 8 == 0 (`relu_` is the in-place form)."""
+    _chk(x, BF16, "dpt_relu.x", 2)
+    _rows(x, "dpt_relu.x", x.shape[0])
+    out = _out_buf(out, BF16, tuple(x.shape), "dpt_relu.out", x.device)
+    if out.data_ptr() == x.data_ptr():
+        raise ValueError("dpt_relu: out must not be x (relu_ is the in-place form)")
+    check(lib.ae_dpt_relu_bf16(_p(x), _p(out), x.numel(), _s()), "ae_dpt_relu_bf16")
+    return out
+
+
+def dpt_tail(y, wp, bp, B, H, W, out=None):
+    """The end of the head on y, the rows [B*H*W, C] of `output_conv2[0]` BEFORE its ReLU: fp32 depth [B, H, W] = relu(sum_c relu(y)[c] wp[c] + bp),
+    fp32 weights wp [C] and bp of one value, fp32 accumulation.  (`DepthAnythingV2.forward`'s own F.relu of this is a no-op.)"""
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"dpt_tail: bad sizes B={B} {H}x{W}")
+    _rows(y, "dpt_tail.y", B * H * W)
+    C = y.shape[1]
+    wp = _dense(wp, torch.float32, "dpt_tail.wp").reshape(-1)
+    bp = _dense(bp, torch.float32, "dpt_tail.bp").reshape(-1)
+    if wp.numel() != C or bp.numel() != 1:
+        raise ValueError(f"dpt_tail: need {C} projection weights and one bias, got {wp.numel()} and {bp.numel()}")
+    out = _out_buf(out, torch.float32, (B, H, W), "dpt_tail.out", y.device)
+    check(lib.ae_dpt_tail_bf16(_p(y), _p(wp), _p(bp), _p(out), B, H, W, C, _s()), "ae_dpt_tail_bf16")
+    return out
+
+
+def depth_resize_minmax(depth, H, W, out=None, minmax=None):
+    """fp32 depth [B, h, w] -> ([B, H, W], minmax [B, 2]): F.interpolate(mode="bilinear", align_corners=True) and each image's (minimum, maximum)
+    of the values written, bit-equal to out.amin((1, 2)) / out.amax((1, 2)) whatever the order the blocks finish in."""
+    depth = _dense(depth, torch.float32, "depth_resize_minmax.depth", 3)
+    B, h, w = depth.shape
+    if B < 1 or B > 65535:
+        raise ValueError(f"depth_resize_minmax: batches of 1 .. 65535 are covered, got {B}")
+    _sides("depth_resize_minmax", h, w, H, W)
+    out = _out_buf(out, torch.float32, (B, H, W), "depth_resize_minmax.out", depth.device)
+    minmax = _out_buf(minmax, torch.float32, (B, 2), "depth_resize_minmax.minmax", depth.device)
+    if out.data_ptr() == depth.data_ptr():
+        raise ValueError("depth_resize_minmax: out must not be the input")
+    check(lib.ae_depth_resize_minmax_f32(_p(depth), _p(out), _p(minmax), B, h, w, H, W, _s()), "ae_depth_resize_minmax_f32")
+    return out, minmax
+
+
+def depth_colorize(depth, minmax, table, out=None):
+    """img2depth's colour image: uint8 [B, H, W, 3] = table[uint8((d - min) / (max - min) * 255.0)], fp32 with IEEE division and truncation; depth
+    fp32 [B, H, W], minmax fp32 [B, 2] on the device (read by the kernel: no host synchronisation), table uint8 [256, 3].  An image whose max equals
+    its min (0 / 0 in the reference) gets table[0] everywhere."""
+    depth = _dense(depth, torch.float32, "depth_colorize.depth", 3)
+    B, H, W = depth.shape
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"depth_colorize: bad sizes {tuple(depth.shape)}")
+    minmax = _dense(minmax, torch.float32, "depth_colorize.minmax", 2)
+    table = _dense(table, torch.uint8, "depth_colorize.table", 2)
+    if tuple(minmax.shape) != (B, 2) or tuple(table.shape) != (256, 3):
+        raise ValueError(f"depth_colorize: need minmax [{B}, 2] and a [256, 3] table, got {tuple(minmax.shape)} and {tuple(table.shape)}")
+    out = _out_buf(out, torch.uint8, (B, H, W, 3), "depth_colorize.out", depth.device)
+    check(lib.ae_depth_colorize_u8(_p(_tmp(depth)), _p(_tmp(minmax)), _p(_tmp(table)), _p(out), B, H, W, _s()), "ae_depth_colorize_u8")
+    return out
+
+
 def rows_to_nchw_out(x, out):
     """channels-last bf16 rows [B*H*W, C] contiguous -> the given [B, C, H, W] buffer (fp32 or bf16, contiguous): `rows_to_nchw` into a
     buffer the caller owns (no allocation)."""
@@ -2484,3 +2604,15 @@ hed_tail = _wrap_profiled(hed_tail, lambda _r, y, wp, bp, B, H, W, pool=True, pr
 hed_fuse = _wrap_profiled(hed_fuse, lambda _r, sides, invert=True, out=None, logits=None, want_logits=False: (
     f"hed_fuse_kernel|B={sides[0].shape[0]} {sides[0].shape[-2]}x{sides[0].shape[-1]}", 0.0,
     float(4 * sum(s.numel() for s in sides) + sides[0].numel() * (1 + 4 * (want_logits or logits is not None)))))
+dpt_reassemble = _wrap_profiled(dpt_reassemble, lambda _r, prod, bias, B, gh, gw, k, out=None: (
+    f"dpt_reassemble_kernel<k={k}>|M={_r.shape[0]} oc={_r.shape[1]}", 0.0, 6.0 * _r.numel()))
+dpt_resize = _wrap_profiled(dpt_resize, lambda _r, x, B, h, w, H, W, addend=None, out=None, relu_out=None, want_relu=False: (
+    f"dpt_resize_kernel<{'add' if addend is not None else 'plain'}{'+relu' if want_relu or relu_out is not None else ''}>|{h}x{w}->{H}x{W} C={x.shape[1]}", 0.0,
+    float(2 * x.numel() + 2 * B * H * W * x.shape[1] * (1 + (addend is not None) + (want_relu or relu_out is not None)))))
+dpt_relu = _wrap_profiled(dpt_relu, lambda _r, x, out=None: (f"dpt_relu_kernel|n={x.numel()}", 0.0, 4.0 * x.numel()))
+dpt_tail = _wrap_profiled(dpt_tail, lambda _r, y, wp, bp, B, H, W, out=None: (
+    f"dpt_tail_kernel|M={y.shape[0]} C={y.shape[1]}", 2.0 * y.numel(), float(2 * y.numel() + 4 * y.shape[0])))
+depth_resize_minmax = _wrap_profiled(depth_resize_minmax, lambda _r, depth, H, W, out=None, minmax=None: (
+    f"depth_resize_minmax_kernel|B={depth.shape[0]} {depth.shape[1]}x{depth.shape[2]}->{H}x{W}", 0.0, float(4 * depth.numel() + 4 * _r[0].numel()), 2))
+depth_colorize = _wrap_profiled(depth_colorize, lambda _r, depth, minmax, table, out=None: (
+    f"depth_colorize_kernel|B={depth.shape[0]} {depth.shape[1]}x{depth.shape[2]}", 0.0, 7.0 * depth.numel()))

@@ -59,6 +59,32 @@ def img2scribble(image_path, output_path, hed_model):
     return output_path
 
 
+def depth_filenames(image_path):
+    """visual_condition_tool.py:117-124: a file (an image, or a .txt list of images, one per line) or a directory searched recursively."""
+    import glob
+    import os
+    if os.path.isfile(image_path):
+        if image_path.endswith('txt'):
+            with open(image_path, 'r') as f:
+                return f.read().splitlines()
+        return [image_path]
+    return glob.glob(os.path.join(image_path, '**/*'), recursive=True)
+
+
+def img2depth(image_path, output_path, depth_anything):
+    """The `visual_depth` branch of visual_condition_tool.py (:111-134) with `depth_anything` an `anyedit_amd.depth_anything_v2.DepthAnythingV2`:
+    the depth of every image named by `image_path`, resized to the image's size, normalised by its own minimum and maximum, truncated to uint8
+    and coloured with matplotlib's `Spectral_r`, written to `output_path` (as in the reference every image goes to the same path: the last one
+    stays).  Files go through PIL (cv2 is not a dependency here).  The network is handed BGR as cv2.imread yields it and `infer_image` flips it
+    back (dpt.py:213).  The reference flips the colour map's RGB rows to BGR (:133) only because cv2.imwrite expects BGR: the file it writes shows
+    the colour map's own RGB colours, so the table is kept in RGB here and saved through PIL unflipped.  Returns `output_path`."""
+    for filename in depth_filenames(image_path):
+        rgb = np.array(Image.open(filename).convert("RGB"))
+        colour = depth_anything.colour_image(np.ascontiguousarray(rgb[:, :, ::-1]))      # cv2.imread's channel order (:129)
+        Image.fromarray(colour).save(output_path)
+    return output_path
+
+
 def maskgeneration(det_model, sam_model, image_path, det_prompt, mask_mode='max', box_threshold=0.25, text_threshold=0.25,
                    target_object=None, device="cuda"):
     """tool.py:166-269.  Returns (mask_pil, image_pil, mask_bbox_pil, union_region); (None, image_pil, None, None) when no box or an

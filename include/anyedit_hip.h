@@ -649,6 +649,31 @@ int ae_hed_tail_bf16(const void* y, const float* wp, const float* bp, float* pro
 int ae_hed_fuse(const float* p0, const float* p1, const float* p2, const float* p3, const float* p4, void* out, float* logits, int B, int H, int W,
                 int invert, void* stream);
 
+/* ---- Depth Anything V2's DPT head (csrc/dpt.hip; AnyEdit_Collection/other_modules/depth_anything_v2/dpt.py, util/blocks.py) and img2depth's colour map
+ * (visual_condition_tool.py:126-134): what stands around the head's convolutions (ae_conv3x3_bf16) and 1x1 products (ae_gemm_bf16).  Bandwidth-bound kernels,
+ * 16 bytes per lane (C % 8 == 0), current stream only, no host synchronisation, no allocation, bit-identical from run to run.
+ * ae_dpt_reassemble_bf16: projects[i] + resize_layers[i] (dpt.py:127-130) after their products.  prod fp32 [B (1 + gh gw), ldp], row = token (the class row of
+ *   every image first), columns (ky k + kx) oc + c: the ConvTranspose2d(kernel = stride = k) product of that token, or with k = 1 the 1x1 product itself.
+ *   out bf16 [B, gh k, gw k, oc] = bf16(prod + bias[c]) at pixel (gy k + ky, gx k + kx); the class rows are not read.  k in {1, 2, 4}; ldp % 4 == 0.
+ * ae_dpt_resize_bf16: F.interpolate(mode="bilinear", align_corners=True) of x bf16 [B, h, w, C] to out bf16 [B, H, W, C], any two sizes with sides of
+ *   1 .. 16384 (a destination side of 1 reads source index 0); source coordinate d (h - 1) / (H - 1) taken in integers.  addend (optional, bf16 [B, H, W, C]) is
+ *   added in fp32 before the single rounding (blocks.py:133).  relu_out (optional, bf16 [B, H, W, C]) receives relu(out).
+ * ae_dpt_relu_bf16: out = max(x, 0) on n bf16 values, out of place (n % 8 == 0); negative values, -0 and negative NaNs become +0.
+ * ae_dpt_tail_bf16: dpt.py:111-114 and :182 on y bf16 [B, H, W, C], the output of output_conv2[0] BEFORE its ReLU: depth fp32 [B, H, W] =
+ *   relu(sum_c relu(y)[c] wp[c] + bp), fp32 weights wp [C], bp [1] (on the device), fp32 accumulation.  The reference's third ReLU (:182) is a no-op on it.
+ * ae_depth_resize_minmax_f32: dpt.py:192: x fp32 [B, h, w] -> out fp32 [B, H, W], bilinear, align_corners=True; minmax fp32 [B, 2] receives each image's
+ *   (minimum, maximum) of the values written, equal to out.amin() / out.amax() bit for bit (integer atomics on the bit patterns; -0 is written as +0).  Two
+ *   launches: the reset of minmax, then the resize.
+ * ae_depth_colorize_u8: visual_condition_tool.py:131-133: out uint8 [B, H, W, 3] = table[uint8((d - min) / (max - min) * 255.0)] in fp32 with IEEE division
+ *   and truncation; minmax fp32 [B, 2] on the device (the buffer ae_depth_resize_minmax_f32 wrote), table uint8 [256, 3].  max == min (0 / 0 in the reference,
+ *   undefined there) gives index 0 at every pixel of that image.                                                                                 */
+int ae_dpt_reassemble_bf16(const float* prod, long ldp, const float* bias, void* out, int B, int gh, int gw, int k, int oc, void* stream);
+int ae_dpt_resize_bf16(const void* x, const void* addend, void* out, void* relu_out, int B, int h, int w, int H, int W, int C, void* stream);
+int ae_dpt_relu_bf16(const void* x, void* out, long n, void* stream);
+int ae_dpt_tail_bf16(const void* y, const float* wp, const float* bp, float* depth, int B, int H, int W, int C, void* stream);
+int ae_depth_resize_minmax_f32(const float* x, float* out, float* minmax, int B, int h, int w, int H, int W, void* stream);
+int ae_depth_colorize_u8(const float* depth, const float* minmax, const void* table, void* out, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
