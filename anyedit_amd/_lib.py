@@ -155,6 +155,9 @@ SIGNATURES = {
     "ae_dpt_tail_bf16": [c_void_p] * 4 + [c_int] * 4 + [c_void_p],
     "ae_depth_resize_minmax_f32": [c_void_p] * 3 + [c_int] * 5 + [c_void_p],
     "ae_depth_colorize_u8": [c_void_p] * 4 + [c_int] * 3 + [c_void_p],
+    "ae_dwconv_rows_bf16": [c_void_p] * 5 + [c_int] * 5 + [c_void_p],
+    "ae_patch2_rows_bf16": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "ae_layernorm_rows_nchw": [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
 }
 _RESTYPES = {"ae_last_error": ctypes.c_char_p, "ae_groupnorm_workspace_floats": c_long, "ae_conv3x3_workspace_floats": c_long,
              "ae_groupnorm_bwd_workspace_floats": c_long, "ae_attn_fp8_workspace_bytes": c_long, "ae_attn_bwd_workspace_floats": c_long,

@@ -435,6 +435,30 @@ def load_depth_anything(model, path_or_state_dict, location="cpu"):
     return layout
 
 
+def load_uniformer(model, path_or_state_dict, location="cpu"):
+    """Fills a `uniformer.UniFormer` from a file or a state dict in one of these forms: the bare backbone (`patch_embed1.proj.weight`, ...), or an
+    mmseg segmentor checkpoint (`{"state_dict": ...}` or flat) whose `backbone.*` entries are taken and whose `decode_head.*` / `auxiliary_head.*`
+    entries are skipped; a `module.` prefix on every key is accepted in either form.  Strict over the backbone's own keys: missing or unexpected
+    ones are reported as `load_state_dict(strict=True)` reports them (`num_batches_tracked` is an ordinary BatchNorm buffer).  Returns the form
+    found."""
+    sd = path_or_state_dict
+    if not isinstance(sd, dict):
+        from anyedit_amd.cldm.model import load_state_dict
+        sd = load_state_dict(sd, location)
+    if "state_dict" in sd and isinstance(sd["state_dict"], dict):
+        sd = sd["state_dict"]
+    layout = "state_dict"
+    if sd and all(k.startswith("module.") for k in sd):
+        sd, layout = {k[len("module."):]: v for k, v in sd.items()}, "module"
+    if any(k.startswith("backbone.") for k in sd):
+        other = [k for k in sd if not k.startswith(("backbone.", "decode_head.", "auxiliary_head."))]
+        if other:
+            raise KeyError(f"load_uniformer: a segmentor checkpoint with entries outside backbone / decode_head / auxiliary_head: {other[:4]}")
+        sd, layout = {k[len("backbone."):]: v for k, v in sd.items() if k.startswith("backbone.")}, layout + "+backbone"
+    model.load_state_dict(sd, strict=True)
+    return layout
+
+
 def load_sd_checkpoint(path, unet=None, vae=None, text_encoder=None, location="cpu"):
     """`load_unet_weights`' sibling for a FULL SD-1.5 state dict (CompVis lineage): routes `model.diffusion_model.*` to `unet`,
     `first_stage_model.*` to `vae` and `cond_stage_model.*` to `text_encoder` (a FrozenCLIPEmbedder); a part given as None is skipped.

@@ -1710,6 +1710,80 @@ def depth_colorize(depth, minmax, table, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- UniFormer backbone (csrc/uniformer.hip)
+DWCONV_KERNELS = (3, 5)
+LN_NCHW_CMAX = 1024
+
+
+def pack_dwconv(w):
+    """Depthwise nn.Conv2d weight [C, 1, k, k] -> fp32 [k*k, C], tap-major (row ky * k + kx): the weight image of `dwconv`.  Stays fp32."""
+    C, one, k, k2 = w.shape
+    if one != 1 or k != k2 or k not in DWCONV_KERNELS:
+        raise ValueError(f"pack_dwconv: expected a depthwise [C, 1, k, k] weight with k in {DWCONV_KERNELS}, got {tuple(w.shape)}")
+    return w.detach().float().reshape(C, k * k).t().contiguous()
+
+
+def pack_patch2(w):
+    """nn.Conv2d(Cin, Cout, kernel_size=2, stride=2) weight [Cout, Cin, 2, 2] -> bf16 [Cout, 4*Cin], column (2 ky + kx) * Cin + cin: the weight
+    image that goes with the rows of `patch2_rows`."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (2, 2):
+        raise ValueError(f"pack_patch2: expected a [Cout, Cin, 2, 2] weight, got {tuple(w.shape)}")
+    return w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1).to(BF16).contiguous()
+
+
+def dwconv(x, w, bias, B, H, W, residual=None, out=None):
+    """Depthwise k x k convolution (stride 1, zero padding k // 2) on bf16 rows [B*H*W, C]: out = bf16(residual + bias + sum_taps w x), fp32
+    accumulation.  w: `pack_dwconv` image, fp32 [k*k, C] with k in {3, 5}; bias fp32 [C]; residual: optional rows, x itself allowed.  Out of
+    place: `out` must not be x."""
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"dwconv: bad sizes B={B} {H}x{W}")
+    _rows(x, "dwconv.x", B * H * W)
+    C = x.shape[1]
+    _chk(w, torch.float32, "dwconv.w", 2)
+    _chk(bias, torch.float32, "dwconv.bias", 1)
+    k = {kk * kk: kk for kk in DWCONV_KERNELS}.get(w.shape[0])
+    if k is None or w.shape[1] != C or not w.is_contiguous() or bias.numel() != C or not bias.is_contiguous():
+        raise ValueError(f"dwconv: need a contiguous [k*k, {C}] weight image with k in {DWCONV_KERNELS} and a bias of {C}, got {tuple(w.shape)} and "
+                         f"{tuple(bias.shape)}")
+    if residual is not None:
+        _rows(residual, "dwconv.residual", B * H * W, C)
+    out = _out_buf(out, BF16, (B * H * W, C), "dwconv.out", x.device)
+    check(lib.ae_dwconv_rows_bf16(_p(x), _p(w), _p(bias), _p(residual), _p(out), B, H, W, C, k, _s()), "ae_dwconv_rows_bf16")
+    return out
+
+
+def patch2_rows(x, B, H, W, out=None):
+    """bf16 rows [B*H*W, C] -> [B*(H//2)*(W//2), 4*C], column (2 ky + kx) * C + c (the order of `pack_patch2`); an odd last row or column is
+    dropped.  Returns (rows, H // 2, W // 2)."""
+    if B < 1 or H < 2 or W < 2:
+        raise ValueError(f"patch2_rows: a {H} x {W} map (batch {B}) is below the 2x2 patch")
+    _rows(x, "patch2_rows.x", B * H * W)
+    C = x.shape[1]
+    out = _out_buf(out, BF16, (B * (H // 2) * (W // 2), 4 * C), "patch2_rows.out", x.device)
+    check(lib.ae_patch2_rows_bf16(_p(x), _p(out), B, H, W, C, _s()), "ae_patch2_rows_bf16")
+    return out, H // 2, W // 2
+
+
+def layernorm_rows_nchw(x, gamma, beta, eps, B, H, W, out=None, rows=None, want_rows=False):
+    """LayerNorm over C of bf16 rows [B*H*W, C], written as fp32 [B, C, H, W] in one launch; with `want_rows` (or a `rows` buffer) the normalised
+    bf16 rows too.  Returns the map, or (map, rows)."""
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"layernorm_rows_nchw: bad sizes B={B} {H}x{W}")
+    _rows(x, "layernorm_rows_nchw.x", B * H * W)
+    C = x.shape[1]
+    if C > LN_NCHW_CMAX:
+        raise ValueError(f"layernorm_rows_nchw: rows of up to {LN_NCHW_CMAX} channels are covered, got {C}")
+    _chk(gamma, torch.float32, "layernorm_rows_nchw.gamma", 1)
+    _chk(beta, torch.float32, "layernorm_rows_nchw.beta", 1)
+    if gamma.numel() != C or beta.numel() != C or not gamma.is_contiguous() or not beta.is_contiguous():
+        raise ValueError(f"layernorm_rows_nchw: gamma and beta need {C} contiguous values")
+    out = _out_buf(out, torch.float32, (B, C, H, W), "layernorm_rows_nchw.out", x.device)
+    if want_rows or rows is not None:
+        rows = _out_buf(rows, BF16, (B * H * W, C), "layernorm_rows_nchw.rows", x.device)
+    check(lib.ae_layernorm_rows_nchw(_p(x), _p(gamma), _p(beta), float(eps), _p(out), _p(rows), B, H, W, C, _s()), "ae_layernorm_rows_nchw")
+    return out if rows is None else (out, rows)
+
+
 def rows_to_nchw_out(x, out):
     """channels-last bf16 rows [B*H*W, C] contiguous -> the given [B, C, H, W] buffer (fp32 or bf16, contiguous): `rows_to_nchw` into a
     buffer the caller owns (no allocation)."""
@@ -2616,3 +2690,11 @@ depth_resize_minmax = _wrap_profiled(depth_resize_minmax, lambda _r, depth, H, W
     f"depth_resize_minmax_kernel|B={depth.shape[0]} {depth.shape[1]}x{depth.shape[2]}->{H}x{W}", 0.0, float(4 * depth.numel() + 4 * _r[0].numel()), 2))
 depth_colorize = _wrap_profiled(depth_colorize, lambda _r, depth, minmax, table, out=None: (
     f"depth_colorize_kernel|B={depth.shape[0]} {depth.shape[1]}x{depth.shape[2]}", 0.0, 7.0 * depth.numel()))
+dwconv = _wrap_profiled(dwconv, lambda _r, x, w, bias, B, H, W, residual=None, out=None: (
+    f"dwconv_rows_kernel<k={int(w.shape[0] ** 0.5 + 0.5)}{',res' if residual is not None else ''}>|B={B} {H}x{W} C={x.shape[1]}", 2.0 * w.shape[0] * x.numel(),
+    float(2 * x.numel() * (2 + (residual is not None and residual is not x)) + 4 * w.numel())))   # algorithmic: x once, out once, a separate residual once
+patch2_rows = _wrap_profiled(patch2_rows, lambda _r, x, B, H, W, out=None: (
+    f"patch2_rows_kernel|B={B} {H}x{W} C={x.shape[1]}", 0.0, 4.0 * _r[0].numel()))
+layernorm_rows_nchw = _wrap_profiled(layernorm_rows_nchw, lambda _r, x, gamma, beta, eps, B, H, W, out=None, rows=None, want_rows=False: (
+    f"layernorm_rows_nchw_kernel{'<+rows>' if want_rows or rows is not None else ''}|B={B} {H}x{W} C={x.shape[1]}", 0.0,
+    float(x.numel() * (2 + 4 + 2 * (want_rows or rows is not None)))))

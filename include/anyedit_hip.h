@@ -674,6 +674,28 @@ int ae_dpt_tail_bf16(const void* y, const float* wp, const float* bp, float* dep
 int ae_depth_resize_minmax_f32(const float* x, float* out, float* minmax, int B, int h, int w, int H, int W, void* stream);
 int ae_depth_colorize_u8(const float* depth, const float* minmax, const void* table, void* out, int B, int H, int W, void* stream);
 
+/* ---- UniFormer backbone (csrc/uniformer.hip; AnyEdit_Collection/other_modules/uniformer/mmseg/models/backbones/uniformer.py): what stands around
+ * the 1x1 convolutions and Linear layers (ae_gemm_bf16 / ae_ln_gemm_bf16), PatchEmbed's LayerNorm (ae_layernorm_bf16) and the global attention
+ * (ae_attn_fwd_bf16).  Activations are channels-last bf16 rows [B, H, W, C], C % 8 == 0.  Bandwidth-bound kernels, 16 bytes per lane, no atomics,
+ * fixed summation orders (bit-identical from run to run, an image's rows do not depend on its batch); current stream only, no host
+ * synchronisation, no allocation.  Each returns AE_ERR_ARG with a message and launches nothing on a null pointer, a non-positive size,
+ * C % 8 != 0, an unsupported k, or a map below the patch.
+ * ae_dwconv_rows_bf16: the depthwise convolutions, nn.Conv2d(dim, dim, k, padding=k/2, groups=dim): CBlock.pos_embed (:66, k = 3), CBlock.attn
+ *   (:70, k = 5), SABlock.pos_embed (:116, k = 3).  w fp32 [k k, C], tap-major (w[(ky k + kx) C + c] = weight[c, 0, ky, kx]); bias fp32 [C];
+ *   residual: optional bf16 [B, H, W, C], may be x itself (`x = x + self.pos_embed(x)`, :78 / :129).  out = bf16(residual + bias + sum w x), fp32
+ *   accumulation from the bias in (ky, kx) order, the residual last.  Zero padding by (y, x) within the image.  Out of place: out aliasing x is
+ *   refused.  k in {3, 5}.
+ * ae_patch2_rows_bf16: the gather of PatchEmbed.proj = nn.Conv2d(kernel_size = stride = 2) (:230, :234) for patch_embed2..4: x bf16 [B, H, W, C] ->
+ *   out bf16 [B, H/2, W/2, 4 C], column (2 ky + kx) C + c = x[b, 2 oy + ky, 2 ox + kx, c]; floor division (an odd last row or column is dropped, as
+ *   the strided convolution drops it).  A copy: exact.  H, W >= 2.
+ * ae_layernorm_rows_nchw: the stage outputs, `norm_i(x.permute(0, 2, 3, 1))` then `.permute(0, 3, 1, 2).contiguous()` (:392-393, :400-401,
+ *   :408-409, :416-417): LayerNorm over C (two-pass fp32 statistics) of x bf16 [B, H, W, C], written as out fp32 [B, C, H, W]; the transposition
+ *   goes through LDS so that both sides are coalesced.  rows: optional bf16 [B, H, W, C] that receives the same values rounded once (x itself is
+ *   allowed).  C <= 1024.                                                                                                                      */
+int ae_dwconv_rows_bf16(const void* x, const float* w, const float* bias, const void* residual, void* out, int B, int H, int W, int C, int k, void* stream);
+int ae_patch2_rows_bf16(const void* x, void* out, int B, int H, int W, int C, void* stream);
+int ae_layernorm_rows_nchw(const void* x, const float* gamma, const float* beta, float eps, float* out, void* rows, int B, int H, int W, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
