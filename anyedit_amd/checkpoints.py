@@ -459,6 +459,34 @@ def load_uniformer(model, path_or_state_dict, location="cpu"):
     return layout
 
 
+def load_segmentor(model, path_or_state_dict, location="cpu"):
+    """Fills a `uniformer.upernet.EncoderDecoder` from an mmseg segmentor checkpoint (`{"state_dict": ..., "meta": ...}` from a file or a dict, or a
+    flat state dict), as `init_segmentor` does: strict over `backbone.*` and `decode_head.*` (missing or unexpected keys are reported as
+    `load_state_dict(strict=True)` reports them); `auxiliary_head.*` entries, the FCN head that never runs at inference, are accepted and skipped; a
+    `module.` prefix on every key is accepted.  `meta['CLASSES']` / `meta['PALETTE']` become `model.CLASSES` / `model.PALETTE` unless the model was
+    built with `classes=` / `palette=`.  Returns the form found."""
+    ck = path_or_state_dict
+    if not isinstance(ck, dict):
+        import torch
+        ck = torch.load(ck, map_location=location, weights_only=False)      # `meta` is read too: load_state_dict would unwrap it away
+    meta = ck.get("meta") if isinstance(ck.get("meta"), dict) else {}
+    sd = ck["state_dict"] if "state_dict" in ck and isinstance(ck["state_dict"], dict) else {k: v for k, v in ck.items() if k != "meta"}
+    layout = "state_dict"
+    if sd and all(k.startswith("module.") for k in sd):
+        sd, layout = {k[len("module."):]: v for k, v in sd.items()}, "module"
+    other = [k for k in sd if not k.startswith(("backbone.", "decode_head.", "auxiliary_head."))]
+    if other:
+        raise KeyError(f"load_segmentor: entries outside backbone / decode_head / auxiliary_head: {other[:4]}")
+    if any(k.startswith("auxiliary_head.") for k in sd):
+        sd, layout = {k: v for k, v in sd.items() if not k.startswith("auxiliary_head.")}, layout + "-auxiliary_head"
+    model.load_state_dict(sd, strict=True)
+    if meta.get("CLASSES") is not None and not model._classes_override:
+        model.CLASSES = list(meta["CLASSES"])
+    if meta.get("PALETTE") is not None and not model._palette_override:
+        model.set_palette(meta["PALETTE"])
+    return layout
+
+
 def load_sd_checkpoint(path, unet=None, vae=None, text_encoder=None, location="cpu"):
     """`load_unet_weights`' sibling for a FULL SD-1.5 state dict (CompVis lineage): routes `model.diffusion_model.*` to `unet`,
     `first_stage_model.*` to `vae` and `cond_stage_model.*` to `text_encoder` (a FrozenCLIPEmbedder); a part given as None is skipped.

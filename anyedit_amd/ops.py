@@ -1784,6 +1784,123 @@ def layernorm_rows_nchw(x, gamma, beta, eps, B, H, W, out=None, rows=None, want_
     return out if rows is None else (out, rows)
 
 
+# --------------------------------------------------------------------------- UPerNet head and the segment map (csrc/upernet.hip)
+UP_MAX_SIDE = 16384
+PPM_MAX_SCALES, PPM_MAX_SCALE = 4, 8
+RESIZE_CONCAT_MAX_SOURCES = 5
+SEG_MAX_CLASSES = 256
+
+
+def fold_bn_after_conv(weight, gamma, beta, mean, var, eps):
+    """A BatchNorm in eval mode directly behind a bias-free convolution (mmcv's ConvModule): s (W x - mean) + beta = (W s) x + (beta - mean s) with
+    s = gamma / sqrt(var + eps) per OUTPUT channel.  weight [Cout, Cin, k, k]; returns (weight scaled per output channel, bias [Cout]) in the dtype
+    of the arguments: the modules fold in fp32, before the rounding to bf16."""
+    s = gamma / torch.sqrt(var + eps)
+    return weight * s.view(-1, *([1] * (weight.dim() - 1))), beta - mean * s
+
+
+def _up_sides(what, *sides):
+    if any(s < 1 or s > UP_MAX_SIDE for s in sides):
+        raise ValueError(f"{what}: sides of 1 .. {UP_MAX_SIDE} are covered, got {sides}")
+
+
+def ppm_pool(x, B, H, W, scales, out=None):
+    """Every nn.AdaptiveAvgPool2d(s) of a pooling pyramid in one launch: bf16 rows [B*H*W, C] -> [B * sum(s*s), C]; within an image scale k's s*s
+    bins follow scale k-1's, row-major.  Up to 4 scales of 1 .. 8 each; fp32 mean, one rounding."""
+    scales = tuple(int(s) for s in scales)
+    if not 1 <= len(scales) <= PPM_MAX_SCALES or any(s < 1 or s > PPM_MAX_SCALE for s in scales):
+        raise ValueError(f"ppm_pool: 1 .. {PPM_MAX_SCALES} pool scales of 1 .. {PPM_MAX_SCALE} each are covered, got {scales}")
+    if B < 1:
+        raise ValueError(f"ppm_pool: bad batch {B}")
+    _up_sides("ppm_pool", H, W)
+    _rows(x, "ppm_pool.x", B * H * W)
+    C = x.shape[1]
+    out = _out_buf(out, BF16, (B * sum(s * s for s in scales), C), "ppm_pool.out", x.device)
+    arr = (ctypes.c_int * len(scales))(*scales)
+    check(lib.ae_ppm_pool_rows_bf16(_p(x), _p(out), B, H, W, C, arr, len(scales), _s()), "ae_ppm_pool_rows_bf16")
+    return out
+
+
+def resize_concat(sources, dst, B, H, W, addend=None):
+    """F.interpolate(mode="bilinear", align_corners=False) of up to five sources into column slices of `dst`, bf16 rows [B*H*W, ld] (contiguous), in
+    one launch.  sources: [(rows, h, w, col, relu), ...] with rows bf16 [B*h*w, C] or [B, h*w, C] (unit inner stride, any row and image stride that is a
+    multiple of 8: a slice of a wider buffer), col
+    the first destination column of the slice, relu: max(tap, 0) as the taps are read.  A source of the destination's size is copied bit for bit.
+    addend: optional bf16 rows [B*H*W, C], with a single source only, added in fp32 before the rounding; it may be the destination's slice itself.
+    The columns of dst outside the slices are not touched.  Returns dst."""
+    n = len(sources)
+    if not 1 <= n <= RESIZE_CONCAT_MAX_SOURCES:
+        raise ValueError(f"resize_concat: 1 .. {RESIZE_CONCAT_MAX_SOURCES} sources per launch, got {n}")
+    if B < 1:
+        raise ValueError(f"resize_concat: bad batch {B}")
+    _up_sides("resize_concat", H, W)
+    _chk(dst, BF16, "resize_concat.dst", 2)
+    if dst.shape[0] != B * H * W or not dst.is_contiguous() or dst.shape[1] % 8:
+        raise ValueError(f"resize_concat: dst must be contiguous rows [{B * H * W}, ld] with ld a multiple of 8, got {tuple(dst.shape)} strides {dst.stride()}")
+    ld = dst.shape[1]
+    spans, views = [], []
+    for i, (rows, h, w, col, relu) in enumerate(sources):
+        _up_sides(f"resize_concat.sources[{i}]", h, w)
+        _chk(rows, BF16, f"resize_concat.sources[{i}]")
+        if rows.dim() == 2 and rows.shape[0] == B * h * w:
+            rows = rows.as_strided((B, h * w, rows.shape[1]), (h * w * rows.stride(0), rows.stride(0), 1), rows.storage_offset())
+        if rows.dim() == 3 and (rows.shape[2] % 8 or rows.shape[2] < 8):
+            raise ValueError(f"resize_concat.sources[{i}]: {rows.shape[2]} channels: the kernel takes 8 channels (16 bytes) per lane, C must be a multiple of 8")
+        if rows.dim() != 3 or tuple(rows.shape[:2]) != (B, h * w) or rows.stride(2) != 1 or rows.stride(1) % 8 or rows.stride(0) % 8:
+            raise ValueError(f"resize_concat.sources[{i}]: expected rows [{B * h * w}, C] or [{B}, {h * w}, C] with unit inner stride and row / image strides "
+                             f"that are multiples of 8, got {tuple(rows.shape)} strides {rows.stride()}")
+        C = rows.shape[2]
+        views.append(rows)
+        if col < 0 or col % 8 or col + C > ld:
+            raise ValueError(f"resize_concat.sources[{i}]: columns {col} .. {col + C} do not fit the destination's {ld} (slices start at multiples of 8)")
+        if any(col < c1 and c0 < col + C for c0, c1 in spans):
+            raise ValueError(f"resize_concat.sources[{i}]: its slice overlaps an earlier one")
+        spans.append((col, col + C))
+    ld_add = 0
+    if addend is not None:
+        if n != 1:
+            raise ValueError("resize_concat: the addend goes with a single source")
+        _chk(addend, BF16, "resize_concat.addend", 2)
+        C = views[0].shape[2]
+        if tuple(addend.shape) != (B * H * W, C) or addend.stride(1) != 1 or addend.stride(0) % 8:
+            raise ValueError(f"resize_concat.addend: expected rows [{B * H * W}, {C}], got {tuple(addend.shape)} strides {addend.stride()}")
+        ld_add = addend.stride(0)
+    vp, ci, cl = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_long * n
+    check(lib.ae_resize_concat_rows_bf16(vp(*[_p(v) for v in views]), ci(*[s[1] for s in sources]), ci(*[s[2] for s in sources]),
+                                         ci(*[v.shape[2] for v in views]), cl(*[v.stride(1) for v in views]), cl(*[v.stride(0) for v in views]), ci(*[s[3] for s in sources]),
+                                         ci(*[1 if s[4] else 0 for s in sources]), n, _p(addend), ld_add, _p(dst), ld, B, H, W, _s()),
+          "ae_resize_concat_rows_bf16")
+    return dst
+
+
+def seg_argmax(logits, ncls, B, h, w, mid, out_size=None, palette=None, labels=None, colours=None):
+    """The end of EncoderDecoder.simple_test in one launch: logits fp32 rows [B*h*w, ld] (classes in the first `ncls` <= 256 columns, ld % 4 == 0; the
+    columns from ncls on are never read) resized (h, w) -> mid = (Hm, Wm) -> out_size = (Ho, Wo) (bilinear, align_corners=False, the second stage
+    skipped when the sizes agree), then the argmax over the classes, the lowest index among equals.  Returns uint8 labels [B, Ho, Wo], or with a
+    uint8 palette [ncls, 3] (labels, colours uint8 [B, Ho, Wo, 3] = palette[label])."""
+    _chk(logits, torch.float32, "seg_argmax.logits", 2)
+    Hm, Wm = mid
+    Ho, Wo = out_size if out_size is not None else mid
+    if B < 1:
+        raise ValueError(f"seg_argmax: bad batch {B}")
+    _up_sides("seg_argmax", h, w, Hm, Wm, Ho, Wo)
+    if not 1 <= ncls <= SEG_MAX_CLASSES:
+        raise ValueError(f"seg_argmax: {ncls} classes: 1 .. {SEG_MAX_CLASSES} are covered (a uint8 label)")
+    if logits.shape[0] != B * h * w or logits.shape[1] < ncls or logits.stride(1) != 1 or logits.stride(0) % 4 or logits.stride(0) < logits.shape[1]:
+        raise ValueError(f"seg_argmax: logits must be rows [{B * h * w}, >= {ncls}] with unit inner stride and a row stride that is a multiple of 4, got "
+                         f"{tuple(logits.shape)} strides {logits.stride()}")
+    if palette is not None:
+        palette = _dense(palette, torch.uint8, "seg_argmax.palette", 2)
+        if tuple(palette.shape) != (ncls, 3):
+            raise ValueError(f"seg_argmax: the palette must be uint8 [{ncls}, 3], got {tuple(palette.shape)}")
+        colours = _out_buf(colours, torch.uint8, (B, Ho, Wo, 3), "seg_argmax.colours", logits.device)
+    elif colours is not None:
+        raise ValueError("seg_argmax: a colour buffer was given without a palette")
+    labels = _out_buf(labels, torch.uint8, (B, Ho, Wo), "seg_argmax.labels", logits.device)
+    check(lib.ae_seg_argmax_u8(_p(logits), logits.stride(0), ncls, _p(_tmp(palette)), _p(labels), _p(colours), B, h, w, Hm, Wm, Ho, Wo, _s()), "ae_seg_argmax_u8")
+    return labels if palette is None else (labels, colours)
+
+
 def rows_to_nchw_out(x, out):
     """channels-last bf16 rows [B*H*W, C] contiguous -> the given [B, C, H, W] buffer (fp32 or bf16, contiguous): `rows_to_nchw` into a
     buffer the caller owns (no allocation)."""
@@ -2698,3 +2815,11 @@ patch2_rows = _wrap_profiled(patch2_rows, lambda _r, x, B, H, W, out=None: (
 layernorm_rows_nchw = _wrap_profiled(layernorm_rows_nchw, lambda _r, x, gamma, beta, eps, B, H, W, out=None, rows=None, want_rows=False: (
     f"layernorm_rows_nchw_kernel{'<+rows>' if want_rows or rows is not None else ''}|B={B} {H}x{W} C={x.shape[1]}", 0.0,
     float(x.numel() * (2 + 4 + 2 * (want_rows or rows is not None)))))
+ppm_pool = _wrap_profiled(ppm_pool, lambda _r, x, B, H, W, scales, out=None: (
+    f"ppm_pool_kernel<{len(tuple(scales))} scales>|B={B} {H}x{W} C={x.shape[1]}", 0.0, float(2 * x.numel() * len(tuple(scales)) + 2 * _r.numel())))   # every scale reads the map once
+resize_concat = _wrap_profiled(resize_concat, lambda _r, sources, dst, B, H, W, addend=None: (
+    f"resize_concat_kernel<{len(sources)} sources{',add' if addend is not None else ''}>|->{H}x{W} ld={dst.shape[1]}", 0.0,
+    float(sum(2 * s[0].numel() + 2 * B * H * W * s[0].shape[-1] for s in sources) + (2 * addend.numel() if addend is not None else 0))))
+seg_argmax = _wrap_profiled(seg_argmax, lambda _r, logits, ncls, B, h, w, mid, out_size=None, palette=None, labels=None, colours=None: (
+    f"seg_argmax_kernel<{'identity' if out_size is None or tuple(out_size) == tuple(mid) else 'two stages'}{',palette' if palette is not None else ''}>|{h}x{w}->{mid[0]}x{mid[1]} "
+    f"ncls={ncls}", 0.0, float(4 * B * h * w * ncls + B * (out_size or mid)[0] * (out_size or mid)[1] * (4 if palette is not None else 1))))   # logits once, labels and colours once

@@ -85,6 +85,19 @@ def img2depth(image_path, output_path, depth_anything):
     return output_path
 
 
+def img2seg(image_path, output_path, model):
+    """The `visual_segment` branch of visual_condition_tool.py with `model` an `anyedit_amd.uniformer.upernet.EncoderDecoder` (UniFormer-S +
+    UPerNet): `inference_segmentor(model, img)` then `show_result_pyplot(model, img, result, get_palette('ade'), opacity=1)`, written to
+    `output_path`.  Files go through PIL (cv2 is not a dependency here); the network is handed BGR as cv2.imread yields it.  The reference hands
+    show_result_pyplot's RGB array to cv2.imwrite, which takes it for BGR: the file it writes shows the palette's colours with red and blue
+    exchanged, and that file is what the edit model was trained on.  Saving `colour_image(...)[..., ::-1]` through PIL writes the same pixels.
+    Returns `output_path`."""
+    rgb = np.array(Image.open(image_path).convert("RGB"))
+    colour = model.colour_image(np.ascontiguousarray(rgb[:, :, ::-1]))                  # cv2.imread's channel order
+    Image.fromarray(np.ascontiguousarray(colour[:, :, ::-1])).save(output_path)
+    return output_path
+
+
 def maskgeneration(det_model, sam_model, image_path, det_prompt, mask_mode='max', box_threshold=0.25, text_threshold=0.25,
                    target_object=None, device="cuda"):
     """tool.py:166-269.  Returns (mask_pil, image_pil, mask_bbox_pil, union_region); (None, image_pil, None, None) when no box or an

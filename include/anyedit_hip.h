@@ -696,6 +696,35 @@ int ae_dwconv_rows_bf16(const void* x, const float* w, const float* bias, const 
 int ae_patch2_rows_bf16(const void* x, void* out, int B, int H, int W, int C, void* stream);
 int ae_layernorm_rows_nchw(const void* x, const float* gamma, const float* beta, float eps, float* out, void* rows, int B, int H, int W, int C, void* stream);
 
+/* ---- UPerNet head and the end of EncoderDecoder.simple_test (csrc/upernet.hip; AnyEdit_Collection/other_modules/uniformer/mmseg/models/decode_heads/
+ * uper_head.py, psp_head.py, decode_head.py and segmentors/encoder_decoder.py): what stands around the head's ConvModules (ae_conv3x3_bf16, ae_gemm_bf16
+ * with EPI_RELU).  Activations are channels-last bf16 rows, C % 8 == 0; every resize is F.interpolate(mode="bilinear", align_corners=False): source
+ * coordinate (d + 0.5) n / N - 0.5 clamped at 0 (taken in integers: ((2 d + 1) n - N) / (2 N)), upper neighbour clamped at n - 1, value
+ * hy (hx p00 + lx p01) + ly (hx p10 + lx p11) in fp32.  Bandwidth-bound kernels, 16 bytes per lane, no atomics, fixed summation orders (bit-identical
+ * from run to run, an image's output does not depend on its batch); current stream only, no host synchronisation, no allocation.  Sides of 1 .. 16384.
+ * Each returns AE_ERR_ARG with a message and launches nothing on a null pointer, a bad size, C % 8 != 0, a misaligned pointer or stride, or an aliasing
+ * it does not cover.
+ * ae_ppm_pool_rows_bf16: every nn.AdaptiveAvgPool2d(s) of PPM (psp_head.py) in one launch.  x bf16 [B, H, W, C]; scales: nscales (1 .. 4) host integers,
+ *   each 1 .. 8; out bf16 [B, sum s s, C]: within an image scale k's s_k s_k bins follow scale k - 1's, row-major.  Bin i of an axis of length n covers
+ *   floor(i n / s) .. ceil((i + 1) n / s) - 1 (bins overlap when s does not divide n and repeat pixels when n < s); the mean is an fp32 sum (pixels
+ *   j, j + S, ... per split, row-major, the splits added in order; S depends on C only) divided by the area, rounded once.
+ * ae_resize_concat_rows_bf16: nsrc (1 .. 5) sources, source i bf16 [B, src_h[i], src_w[i], src_c[i]] with row stride src_ld[i] and image stride src_img[i] (elements), resized to
+ *   H x W and written to columns dst_col[i] .. dst_col[i] + src_c[i] of dst bf16 [B, H, W] rows of stride ld_dst; the other columns of dst are not
+ *   touched.  relu[i] != 0: max(tap, 0) on every tap as it is read (a ConvModule's activation on an output only this kernel reads).  A source of the
+ *   destination's size is copied bit for bit (with relu: negative values, -0 and negative NaNs become +0).  addend: optional bf16 rows of stride ld_add,
+ *   with nsrc == 1 only, added in fp32 before the single rounding; it may be dst's own slice (`laterals[i - 1] += resize(laterals[i])`,
+ *   uper_head.py).  No source may overlap dst.  Strides are multiples of 8 below 2^31 (src_img[i] is not read when B == 1).  The eight arrays are host arrays of nsrc entries.
+ * ae_seg_argmax_u8: logits fp32 [B, h, w] rows of stride ld (ld % 4 == 0), classes in columns 0 .. ncls - 1 (ncls <= 256; columns from ncls on are never
+ *   read).  Per output pixel of [B, Ho, Wo]: whole_inference's resize (Hm, Wm) -> (Ho, Wo) of encode_decode's resize (h, w) -> (Hm, Wm) (each of the outer
+ *   four taps is a four-tap fp32 value; with (Hm, Wm) == (Ho, Wo) the outer stage is the identity and is skipped), then the argmax over the classes, the
+ *   lowest index among equal values.  labels uint8 [B, Ho, Wo]; with palette uint8 [ncls, 3] (on the device) also colours uint8 [B, Ho, Wo, 3] =
+ *   palette[label] (both or neither).  inference()'s softmax is left out: it is strictly increasing per pixel.                                  */
+int ae_ppm_pool_rows_bf16(const void* x, void* out, int B, int H, int W, int C, const int* scales, int nscales, void* stream);
+int ae_resize_concat_rows_bf16(const void* const* src, const int* src_h, const int* src_w, const int* src_c, const long* src_ld, const long* src_img,
+                               const int* dst_col, const int* relu, int nsrc, const void* addend, long ld_add, void* dst, long ld_dst, int B, int H, int W, void* stream);
+int ae_seg_argmax_u8(const float* logits, long ld, int ncls, const void* palette, void* labels, void* colours, int B, int h, int w, int Hm, int Wm, int Ho,
+                     int Wo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
