@@ -480,22 +480,28 @@ inline int sam_occ() {
     return v;
 }
 
-template <int D, int QF, bool DBUF, int NW = 4>
+// REL / SEG2K: whether ae_attn_fwd_bf16 can send a rel-pos bias / a second segment to this (D, QF, NW) at all; a form it never sends is
+// not compiled (tests/route_cases.py, ATTN_GENERAL_LEDGER: every instantiation here is one some environment reaches)
+template <int D, int QF, bool DBUF, int NW = 4, bool REL = true, bool SEG2K = true>
 int launch_attn(const AttnArgs& a, hipStream_t stream) {
     constexpr int QB = NW * 16 * QF;
     constexpr int NT = 64 * NW;
     const long blocks = (long)((a.Nq + QB - 1) / QB) * a.B * a.H;
     dim3 grid((unsigned)blocks), block(NT);
     if (a.rel_h && a.key_mask) { ae_set_error("ae_attn_fwd_bf16: rel-pos bias together with key_mask is not supported"); return AE_ERR_UNSUPPORTED; }
+    if (!REL && a.rel_h) { ae_set_error("ae_attn_fwd_bf16: no rel-pos variant of head_dim %d with %d query fragments on %d waves", D, QF, NW); return AE_ERR_UNSUPPORTED; }
+    if (!SEG2K && a.k2) { ae_set_error("ae_attn_fwd_bf16: no two-segment variant of head_dim %d with %d query fragments on %d waves", D, QF, NW); return AE_ERR_UNSUPPORTED; }
     if (a.k2) {
-        if constexpr (D <= 96 || (D == 160 && QF == 1)) hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 0, false, true>), grid, block, 0, stream, a);
-    } else if (a.rel_h && NW == 8 && a.kW == KT && a.Nk % KT == 0 && sam_occ() == 4) {
-        hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 2, false, false, NW == 8>), grid, block, 0, stream, a);
-    } else if (a.rel_h && NW == 8 && !(a.kW == KT && a.Nk % KT == 0) && sam_occ() >= 1) {
-        hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 1, false, false, NW == 8>), grid, block, 0, stream, a);
-    } else if (a.rel_h && a.kW == KT && a.Nk % KT == 0) hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 2, false>), grid, block, 0, stream, a);
-    else if (a.rel_h) hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 1, false>), grid, block, 0, stream, a);
-    else if (a.key_mask) hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 0, true>), grid, block, 0, stream, a);
+        if constexpr (SEG2K && (D <= 96 || (D == 160 && QF == 1))) hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 0, false, true>), grid, block, 0, stream, a);
+    } else if (a.rel_h) {
+        if constexpr (REL) {
+            const bool row_tiles = a.kW == KT && a.Nk % KT == 0;   // one key tile = one row of the key grid: BIAS 2
+            if (NW == 8 && row_tiles && sam_occ() == 4) hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 2, false, false, NW == 8>), grid, block, 0, stream, a);
+            else if (NW == 8 && !row_tiles && sam_occ() >= 1) hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 1, false, false, NW == 8>), grid, block, 0, stream, a);
+            else if (row_tiles) hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 2, false>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 1, false>), grid, block, 0, stream, a);
+        }
+    } else if (a.key_mask) hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 0, true>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((attn_kernel<D, QF, NW, DBUF, 0, false>), grid, block, 0, stream, a);
     return ae_check_launch("ae_attn_fwd_bf16");
 }
@@ -547,6 +553,14 @@ extern "C" int ae_attn_fwd_bf16(const void* q, const void* k, const void* v, voi
         const int rc = ae_attn_fast_launch(a, D, s);
         if (rc != AE_ERR_UNSUPPORTED) return rc;
     }
+    // attn_kernel addresses one (batch, head) image of K / V through a buffer descriptor with 32-bit byte offsets: its extent must fit
+    const long kv_lim = 1L << 31;
+    if (((long)(Nk - 1) * k_sn + D) * 2 >= kv_lim || ((long)(Nk - 1) * v_sn + D) * 2 >= kv_lim ||
+        (k2 && (((long)(Nk2 - 1) * k2_sn + D) * 2 >= kv_lim || ((long)(Nk2 - 1) * v2_sn + D) * 2 >= kv_lim))) {
+        ae_set_error("ae_attn_fwd_bf16: the K / V image of one (batch, head) spans 2^31 bytes or more (Nk=%d k_sn=%ld v_sn=%ld Nk2=%d k2_sn=%ld v2_sn=%ld, "
+                     "head_dim %d): the kernel's 32-bit byte offsets stop at 2^31 - 1", Nk, k_sn, v_sn, Nk2, k2_sn, v2_sn, D);
+        return AE_ERR_UNSUPPORTED;
+    }
     static const int qf40 = env_int("AE_ATTN_QF40", 4);  // tuning knob (A/B on hardware): query fragments per wave for D=40
     static const int w8 = env_int("AE_ATTN_W8", 0);      // tuning knob: 8 waves x 1 query fragment instead of 4 x 2
     // tuning knob: short K/V (cross-attention to 77 text + adapter tokens): 1 query fragment per wave -> half the registers, twice the
@@ -560,23 +574,23 @@ extern "C" int ae_attn_fwd_bf16(const void* q, const void* k, const void* v, voi
         case 32: return launch_attn<32, 2, true>(a, s);
         case 40:
             if (w8) return launch_attn<40, 1, true, 8>(a, s);
-            if (short_kv) return launch_attn<40, 1, true>(a, s);
+            if (short_kv) return launch_attn<40, 1, true, 4, false>(a, s);   // (short_kv: no rel-pos bias)
             // (2 fragments per wave under a 168-VGPR cap — 153 VGPRs, no spills, three resident blocks per CU — was A/B-ed against the
             // 4-fragment variant: 18.11 vs 18.04 ms per step; the K/V reuse of 4 fragments is worth more than the third block)
             // 64 queries per wave halve the K/V staging and K-fragment reads per query (514 vs 547 us at N = 4096); only for long
             // self-attention: the two-segment variant would spill at 4 fragments, and short K/V has nothing to amortise
-            return (qf40 == 4 && Nq > 1024 && Nk >= 1024 && !k2) ? launch_attn<40, 4, true>(a, s) : launch_attn<40, 2, true>(a, s);
+            return (qf40 == 4 && Nq > 1024 && Nk >= 1024 && !k2) ? launch_attn<40, 4, true, 4, true, false>(a, s) : launch_attn<40, 2, true>(a, s);
         case 48: return launch_attn<48, 2, true>(a, s);
         case 64: return launch_attn<64, 2, true>(a, s);
         // SAM (rel-pos bias): 8 waves x 1 query fragment keeps the bias registers + softmax state under 256 VGPRs without spills
         case 80:
-            if (short_kv) return launch_attn<80, 1, true>(a, s);
-            return (w8 || rel_h) ? launch_attn<80, 1, true, 8>(a, s) : launch_attn<80, 2, true>(a, s);
+            if (short_kv) return launch_attn<80, 1, true, 4, false>(a, s);
+            return (w8 || rel_h) ? launch_attn<80, 1, true, 8>(a, s) : launch_attn<80, 2, true, 4, false>(a, s);
         case 96: return launch_attn<96, 2, true>(a, s);
         case 128: return launch_attn<128, 2, false>(a, s);
         // two segments at d = 160 (the 16x16-level cross-attention + expert tokens): one query fragment per wave keeps both output
         // accumulators in registers (256 + 170 of the wave's 512, no spills; two fragments spill 78)
-        case 160: return (short_kv || k2) ? launch_attn<160, 1, false>(a, s) : launch_attn<160, 2, false>(a, s);
+        case 160: return (short_kv || k2) ? launch_attn<160, 1, false, 4, false>(a, s) : launch_attn<160, 2, false>(a, s);
         default:
             ae_set_error("ae_attn_fwd_bf16: unsupported head_dim %d (supported: 8,16,32,40,48,64,80,96,128,160)", D);
             return AE_ERR_UNSUPPORTED;

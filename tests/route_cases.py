@@ -1,6 +1,7 @@
 """Route cases and the route ledger of gemm_conv.hip / attention_fast.hip (CASES, LEDGER: tools/route_check.py), of norm.hip (NORM_CASES,
-NORM_LEDGER: tools/norm_route_check.py) and of gemm_rowpanel.hip / ff_fused.hip (ROWPANEL_CASES, ROWPANEL_LEDGER:
-tools/rowpanel_route_check.py), shared with tests/test_kernel_routes.py.
+NORM_LEDGER: tools/norm_route_check.py), of gemm_rowpanel.hip / ff_fused.hip (ROWPANEL_CASES, ROWPANEL_LEDGER:
+tools/rowpanel_route_check.py) and of attention.hip (ATTN_GENERAL_CASES, ATTN_GENERAL_LEDGER: tools/attn_general_route_check.py; the
+template-argument order and the case options stand above the cases), shared with tests/test_kernel_routes.py.
 
 CASES: one dict per GPU case (op + shape + options); tools/route_check.py builds the seeded operands, runs the op through `ops`, records the
 kernels it launched and checks the output element by element (see that script's docstring for the bound).
@@ -9,7 +10,11 @@ LEDGER / NORM_LEDGER: one row per kernel instantiation of the three files in the
 (`gemm_kernel<192, 320, 1, 2, 4, true, 1, 2, false, 0, 4, 0>`: BM, BN, AMODE (0 dense, 1 conv), WAVES_M, WAVES_N, GLDS, WAVES_K, STAGES,
 CS, LAB, WA, XE; `attn_fast_kernel<D, OCC, SEG2, ABL, BIAS, QG, VSPLIT, SKV, NWV, SKT>`; `attn_pipe_kernel<D, KT, PV16>`).  Each row is
   ("default", [case ids])   reached with no AE_* variable set, by every case listed.
-The default build compiles nothing that no case reaches.
+ATTN_GENERAL_LEDGER alone also has rows of the form
+  ("env", {"AE_ATTN_FAST": "0", ...}, [case ids])   reached by every case listed in a process with every AE_* variable removed and exactly
+                                                    those set: the variants that only a tuning knob of attention.hip selects.
+The default build compiles nothing that no case reaches: every instantiation is a `default` row, or an `env` row whose environment the
+test starts a child process for; what no environment reaches is not compiled.
 """
 
 # --------------------------------------------------------------------------------------------------- cases
@@ -502,3 +507,177 @@ ROWPANEL_LEDGER = {
 def expected_kernels(case_id):
     """ledger keys whose `default` row lists this case"""
     return sorted(k for led in (LEDGER, NORM_LEDGER, ROWPANEL_LEDGER) for k, (kind, v) in led.items() if kind == "default" and case_id in v)
+
+
+# --------------------------------------------------------------------------------------------------- attention.hip: cases
+# The general attn_kernel<D, QF, NW, DBUF, BIAS, HAS_MASK, SEG2, OCC4> (tools/attn_general_route_check.py):
+#   D head dim; QF 16-row query fragments per wave; NW waves per block (a block owns QB = 16 QF NW query rows); DBUF double-buffered K/V tiles
+#   (every head dim below 128); BIAS 0 none, 1 rel-pos bias by look-up (from LDS when kH, kW <= 32, else from global memory), 2 rel-pos bias with
+#   one key-grid row per 64-key tile (kW == 64, Nk % 64 == 0); HAS_MASK key mask; SEG2 second key/value segment; OCC4 the 128-VGPR cap of the
+#   rel-pos variants on eight waves.
+# A case is an `attn` case with: env (a name of ATTN_GENERAL_ENVS: the AE_* variables of the child process that runs it), qf / nw / occ (the
+# variant the library must pick for it there), and the options
+#   mask  "rand" | "lead" (keys 0..63 removed) | "trail" (the last whole 64-key tile removed) | "tailkey" (a key inside the ragged last tile
+#         removed) | "all" (sample 0 loses every key, sample 1 takes a random mask); the mask is [B, Nk], shared by a sample's heads, and sample 1
+#         always differs from sample 0
+#   gate  per-sample out_scale;  onto  accumulate=True onto a pre-filled output;  o_pad  output row stride = H D + o_pad
+#   nk2   second segment of nk2 keys with a per-sample scale2;  rel  (kH, kW) rel-pos bias, Nk = kH kW
+# Nq sits around QB (1, QB - 1, QB, QB + 1), Nk around the 64-key tile (1, 63, 64, 65, 128, 129, 193: no ragged tile, a ragged tile of one key,
+# an odd and an even tile count for the double buffer).  B H = 6 (2 for the QF = 4 cases, which the dispatch takes from Nq > 1024, Nk >= 1024).
+ATTN_GENERAL_ENVS = {
+    "default": {},
+    "nofast": {"AE_ATTN_FAST": "0"},                                                          # head dims 40 / 80 / 160 stay in attention.hip
+    "w8": {"AE_ATTN_FAST": "0", "AE_ATTN_W8": "1"},                                           # eight waves of one fragment at d = 40 / 80
+    "w8_occ4": {"AE_ATTN_FAST": "0", "AE_ATTN_W8": "1", "AE_ATTN_SAM_OCC": "4"},              # + the VGPR cap on the row-per-tile bias form
+    "w8_occ0": {"AE_ATTN_FAST": "0", "AE_ATTN_W8": "1", "AE_ATTN_SAM_OCC": "0"},              # + no VGPR cap on the look-up bias form
+    "shortk": {"AE_ATTN_FAST": "0", "AE_ATTN_SHORTK_QF1": "1"},                               # one fragment per wave under 256 keys
+}
+_AG_MASKS_ALL = ("rand", "lead", "trail", "tailkey", "all")
+_AG_REL_LDS = ((14, 14), (3, 5), (5, 3), (1, 31), (32, 32))
+_AG_REL_GLOBAL = ((2, 40), (40, 2), (33, 3))
+_AG_REL_ROWS = ((1, 64), (3, 64))
+
+
+def _ag(tag, env, D, Nq, Nk, qf, nw, i=0, **kw):
+    kw.setdefault("B", 2)
+    kw.setdefault("H", 3)
+    kw.setdefault("lay", ("bhnd", "qkv")[i % 2])
+    return dict(id=f"ag_{env}_d{D}q{qf}w{nw}_{tag}", op="attn", env=env, D=D, Nq=Nq, Nk=Nk, qf=qf, nw=nw, **kw)
+
+
+def _ag_group(env, D, qf, nw, kinds, full=False, occ1=False, occ2=False, masks=None, rel1=None, rel2=None):
+    """the cases of one (environment, D, QF, NW); kinds: which of plain / mask / rel1 / rel2 / seg2 / gate the library sends there in that
+    environment; full: the whole edge set (else the reduced one: every row still gets a ragged last query block and every hazard of its kind)"""
+    QB, out = 16 * qf * nw, []
+    a = lambda tag, Nq, Nk, i=0, **kw: out.append(_ag(tag, env, D, Nq, Nk, qf, nw, i, **kw))
+    if "plain" in kinds:
+        edges = [(1, 1), (QB - 1, 63), (QB, 64), (QB + 1, 65), (QB // 2 + 1, 128), (QB + 1, 129), (QB + 2, 193)]
+        for i, (Nq, Nk) in enumerate(edges if full else edges[:1] + edges[3:]):
+            a(f"n{Nq}k{Nk}", Nq, Nk, i)
+    if "mask" in kinds:
+        for i, m in enumerate(masks or (_AG_MASKS_ALL if full else ("rand", "lead"))):
+            Nq, Nk = {"rand": (QB - 1, 193), "lead": (QB + 1, 150), "trail": (QB + 1, 150), "tailkey": (QB, 150), "all": (QB + 1, 129)}[m]
+            a(f"mask_{m}", Nq, Nk, i, mask=m)
+        if full:
+            a("mask_rand_k64", QB + 1, 64, 1, mask="rand")
+            a("mask_lead_k65", 1, 65, 0, mask="lead")       # one live key behind a dead tile
+    if "rel1" in kinds:
+        grids = rel1 if rel1 is not None else (_AG_REL_LDS + _AG_REL_GLOBAL if full else ((5, 3), (3, 5), (33, 3)))
+        for i, (kH, kW) in enumerate(grids):
+            a(f"rel{kH}x{kW}", (QB + 3, QB - 1, 1, QB + 1)[i % 4], kH * kW, i, rel=(kH, kW), occ=occ1)
+    if "rel2" in kinds:
+        for i, (kH, kW) in enumerate(rel2 if rel2 is not None else _AG_REL_ROWS):
+            a(f"rel{kH}x{kW}", (QB + 1, QB - 1)[i % 2], kH * kW, i, rel=(kH, kW), occ=occ2)
+    if "seg2" in kinds:
+        for i, nk2 in enumerate((1, 8, 64, 65) if full else (8, 65)):
+            a(f"seg2_{nk2}", (QB + 1, QB - 1, QB, 1)[i % 4], (77, 129, 64, 193)[i % 4], i, nk2=nk2)
+    if "gate" in kinds:
+        for i, (g, o, pad) in enumerate(((True, False, 0), (False, True, 0), (True, True, 8), (False, False, 8))):
+            for Nq in (QB, QB + 1):
+                a(("gate" if g else "") + ("onto" if o else "") + (f"pad{pad}" if pad else "") + f"_n{Nq}", Nq, (129, 65)[i % 2], i, gate=g, onto=o, o_pad=pad)
+    return out
+
+
+def _ag_qf4(env, kinds):
+    """d = 40 with four fragments per wave (QB = 256): the dispatch wants Nq > 1024 and Nk >= 1024"""
+    out = []
+    a = lambda tag, Nq, Nk, **kw: out.append(_ag(tag, env, 40, Nq, Nk, 4, 4, B=2, H=1, **kw))
+    if "plain" in kinds:
+        a("n1025k1024", 1025, 1024, lay="qkv")
+        a("n1281k1087", 1281, 1087, lay="bhnd")
+    if "mask" in kinds:
+        a("mask_lead", 1281, 1087, mask="lead", lay="qkv")
+        a("mask_tailkey", 1281, 1087, mask="tailkey", lay="bhnd")
+        a("mask_rand", 1025, 1024, mask="rand", lay="bhnd")
+        a("mask_trail", 1025, 1024, mask="trail", lay="qkv")
+        a("mask_all", 1025, 1087, mask="all", lay="bhnd")
+    if "rel1" in kinds:
+        a("rel32x32", 1025, 1024, rel=(32, 32), lay="bhnd")
+        a("rel33x32", 1281, 1056, rel=(33, 32), lay="qkv")
+        a("rel4x257", 1027, 1028, rel=(4, 257), lay="bhnd")
+    if "rel2" in kinds:
+        a("rel16x64", 1025, 1024, rel=(16, 64), lay="qkv")
+        a("rel17x64", 1281, 1088, rel=(17, 64), lay="bhnd")
+    return out
+
+
+ATTN_GENERAL_CASES = (
+    # ---- no AE_* variable: every head dim attention_fast.hip does not own, and what it declines of 40 / 80 / 160 (a key mask; a rel-pos bias at
+    #      d = 40 / 160, or at d = 80 on a grid that is neither kW == 64 nor within 16 x 16, or together with out_scale / accumulate)
+    _ag_group("default", 8, 2, 4, ("plain", "mask", "rel1", "rel2", "seg2"), masks=("rand", "lead", "all"))
+    + _ag_group("default", 16, 2, 4, ("plain", "mask", "rel1", "rel2", "seg2"))
+    + _ag_group("default", 32, 2, 4, ("plain", "mask", "rel1", "rel2", "seg2", "gate"), full=True)
+    + _ag_group("default", 48, 2, 4, ("plain", "mask", "rel1", "rel2", "seg2"), masks=("rand", "lead", "tailkey"), rel1=_AG_REL_LDS + _AG_REL_GLOBAL)
+    + _ag_group("default", 64, 2, 4, ("plain", "mask", "rel1", "rel2", "seg2", "gate"), full=True)
+    + _ag_group("default", 96, 2, 4, ("plain", "mask", "rel1", "rel2", "seg2"))
+    + _ag_group("default", 128, 2, 4, ("plain", "mask", "rel1", "rel2"), masks=("rand", "lead", "trail"))
+    + _ag_group("default", 128, 2, 4, ("plain",), full=True)[1:3]                                      # the single-buffer loop at 63 / 64 keys
+    + _ag_group("default", 40, 2, 4, ("mask", "rel1", "rel2"), full=True)
+    + _ag_qf4("default", ("mask", "rel1", "rel2"))
+    + _ag_group("default", 80, 2, 4, ("mask",), full=True)
+    + _ag_group("default", 80, 1, 8, ("rel1",), occ1=True, rel1=((1, 31), (32, 32), (17, 5)) + _AG_REL_GLOBAL)
+    + [_ag("rel3x64_gate", "default", 80, 129, 192, 1, 8, rel=(3, 64), gate=True, occ=False),
+       _ag("rel1x64_onto", "default", 80, 127, 64, 1, 8, rel=(1, 64), onto=True, occ=False)]
+    + _ag_group("default", 160, 2, 4, ("mask", "rel1", "rel2"), full=True)
+    # ---- AE_ATTN_FAST=0: the plain and two-segment forms of 40 / 80 / 160
+    + _ag_group("nofast", 40, 2, 4, ("plain", "seg2"), full=True)
+    + _ag_qf4("nofast", ("plain",))
+    + _ag_group("nofast", 80, 2, 4, ("plain", "seg2"), full=True)
+    + _ag_group("nofast", 160, 2, 4, ("plain",), full=True)
+    + _ag_group("nofast", 160, 1, 4, ("seg2",), full=True)
+    # ---- + AE_ATTN_W8=1: eight waves of one fragment
+    + _ag_group("w8", 40, 1, 8, ("plain", "mask", "seg2", "rel1", "rel2"), occ1=True, masks=("rand", "lead", "tailkey", "all"))
+    + _ag_group("w8", 80, 1, 8, ("plain", "mask", "seg2"), masks=("rand", "lead", "tailkey"))
+    + _ag_group("w8_occ4", 40, 1, 8, ("rel2",), occ2=True)
+    + _ag_group("w8_occ4", 80, 1, 8, ("rel2",), occ2=True)
+    + _ag_group("w8_occ0", 40, 1, 8, ("rel1",), rel1=((14, 14), (3, 5), (1, 31), (40, 2)))
+    + _ag_group("w8_occ0", 80, 1, 8, ("rel1",), rel1=((14, 14), (5, 3), (32, 32), (33, 3)))
+    # ---- AE_ATTN_FAST=0 AE_ATTN_SHORTK_QF1=1: one fragment per wave on four waves (QB = 64) under 256 keys
+    + _ag_group("shortk", 40, 1, 4, ("plain", "mask", "seg2"), full=True)
+    + _ag_group("shortk", 80, 1, 4, ("plain", "mask", "seg2"), masks=("rand", "lead", "tailkey"))
+    + _ag_group("shortk", 160, 1, 4, ("plain", "mask"), masks=("rand", "lead", "tailkey"))
+)
+ATTN_GENERAL_CASE_IDS = [c["id"] for c in ATTN_GENERAL_CASES]
+
+
+def attn_general_key(c):
+    """the instantiation a case of ATTN_GENERAL_CASES declares"""
+    rel = c.get("rel")
+    bias = 0 if not rel else 2 if rel[1] == 64 and c["Nk"] % 64 == 0 else 1
+    args = (c["D"], c["qf"], c["nw"], c["D"] < 128, bias, bool(c.get("mask")), bool(c.get("nk2")), bool(c.get("occ")))
+    return "attn_kernel<" + ", ".join(str(x).lower() for x in args) + ">"
+
+
+# --------------------------------------------------------------------------------------------------- attention.hip: ledger
+# One row per attn_kernel instantiation of the build.  A row is ("default", [case ids]) — reached with every AE_* variable removed — or
+# ("env", {variables}, [case ids]) — reached in a child process with every AE_* variable removed and exactly those set, because only a tuning
+# knob of attention.hip sends anything there.  All cases of a row run in one environment.
+def _ag_row(key):
+    cases = [c for c in ATTN_GENERAL_CASES if attn_general_key(c) == key]
+    envs = sorted({c["env"] for c in cases})
+    assert len(envs) <= 1, (key, envs)
+    ids = [c["id"] for c in cases]
+    return ("default", ids) if envs in ([], ["default"]) else ("env", dict(ATTN_GENERAL_ENVS[envs[0]]), ids)
+
+
+def _agk(D, qf, nw, bias=0, mask=False, seg2=False, occ4=False):
+    return attn_general_key(dict(D=D, qf=qf, nw=nw, Nk=64, rel=(None, (3, 5), (1, 64))[bias], mask=mask, nk2=seg2, occ=occ4))
+
+
+_AG_FORMS = dict(plain=dict(), mask=dict(mask=True), rel1=dict(bias=1), rel2=dict(bias=2), seg2=dict(seg2=True))
+_AG_ROWS = (
+    [(D, 2, 4, f) for D in (8, 16, 32, 40, 48, 64, 96) for f in ("plain", "mask", "rel1", "rel2", "seg2")]
+    + [(D, 2, 4, f) for D in (128, 160) for f in ("plain", "mask", "rel1", "rel2")]
+    + [(40, 4, 4, f) for f in ("plain", "mask", "rel1", "rel2")]
+    + [(80, 2, 4, f) for f in ("plain", "mask", "seg2")]
+    + [(D, 1, 4, f) for D in (40, 80, 160) for f in ("plain", "mask", "seg2")]
+    + [(D, 1, 8, f) for D in (40, 80) for f in ("plain", "mask", "rel1", "rel2", "seg2")]
+)
+ATTN_GENERAL_LEDGER = {_agk(D, qf, nw, **_AG_FORMS[f]): None for D, qf, nw, f in _AG_ROWS}
+ATTN_GENERAL_LEDGER.update({_agk(D, 1, 8, bias=b, occ4=True): None for D in (40, 80) for b in (1, 2)})
+ATTN_GENERAL_LEDGER = {k: _ag_row(k) for k in ATTN_GENERAL_LEDGER}
+
+
+def attn_general_expected(case_id):
+    """ATTN_GENERAL_LEDGER keys whose row lists this case"""
+    return sorted(k for k, row in ATTN_GENERAL_LEDGER.items() if case_id in row[-1])

@@ -1,7 +1,7 @@
-"""Route ledger of gemm_conv.hip / attention_fast.hip / norm.hip / gemm_rowpanel.hip / ff_fused.hip (tests/route_cases.py) and the GPU route
-cases behind it.
+"""Route ledger of gemm_conv.hip / attention_fast.hip / norm.hip / gemm_rowpanel.hip / ff_fused.hip / attention.hip (tests/route_cases.py) and
+the GPU route cases behind it.
 
-CPU: the set of kernel instantiations the default build compiles — hipcc's device-only LLVM IR of the five sources with the library's flags
+CPU: the set of kernel instantiations the default build compiles — hipcc's device-only LLVM IR of the six sources with the library's flags
 (at -O0: which kernels a translation unit emits does not depend on the optimisation level) — must equal the ledger's keys, in both
 directions, so an instantiation that is added or removed fails here until someone classifies it.
 
@@ -13,6 +13,9 @@ The cases of norm.hip run the same way in a child process of their own (tools/no
 The cases of gemm_rowpanel.hip / ff_fused.hip (tools/rowpanel_route_check.py, test_rowpanel_route_cases_on_gpu) take two children: the
 small ones reach the kernels through the library's test hook, AE_ROWPANEL_ANY_M=1 in that child's environment only; the plan threshold
 (192 blocks of 192 rows run the kernels, 191 run the tiled gemm_kernel) is crossed from both sides with every AE_* variable removed.
+The cases of attention.hip's general attn_kernel (tools/attn_general_route_check.py, test_attn_general_route_cases_on_gpu) take one child per
+environment of route_cases.ATTN_GENERAL_ENVS, one after another: the `default` rows with every AE_* variable removed, each `env` row with
+exactly its row's variables set (attention.hip reads those tuning knobs once per process).
 """
 import json
 import os
@@ -30,11 +33,13 @@ import route_cases as RC  # noqa: E402
 NORM_FAMILIES = ("gn_slab_kernel", "gn_apply_kernel", "gnb_slab_kernel", "layernorm_rows_kernel", "layernorm_kernel", "layernorm_window_kernel",
                  "layernorm_narrow_kernel", "layernorm_bwd_kernel")
 ROWPANEL_FAMILIES = ("gemm_rowpanel_kernel", "ff_fused_kernel")
-FAMILY_RE = re.compile(r"^void (?:\(anonymous namespace\)::)?(gemm_kernel|attn_fast_kernel|attn_pipe_kernel|" + "|".join(NORM_FAMILIES + ROWPANEL_FAMILIES) + r")<([^<>]*)>\(")
+FAMILY_RE = re.compile(r"^void (?:\(anonymous namespace\)::)?(gemm_kernel|attn_fast_kernel|attn_pipe_kernel|attn_kernel|" + "|".join(NORM_FAMILIES + ROWPANEL_FAMILIES) + r")<([^<>]*)>\(")
 NORM_PLAIN = ("gn_stats_kernel", "gn_finalize_kernel", "gn_finalize_cs_kernel", "gnb_partial_kernel", "gnb_finalize_kernel", "gnb_apply_kernel",
               "layernorm_param_grad_kernel")
 PLAIN = ("splitk_reduce_kernel", "colstats_kernel") + NORM_PLAIN
 ROWPANEL_CHILD_TIMEOUT = 120    # seconds for each child of tools/rowpanel_route_check.py; measured on the MI355X: 5.1 s (hook, 45 cases) and 8.8 s (default, 4 cases at M = 36673)
+ATTN_GENERAL_CHILD_TIMEOUT = 60    # seconds for each child of tools/attn_general_route_check.py; measured on the MI355X, whole children: 5.5 s (default,
+                                   # 209 cases), 4.3 s (nofast, 35), 4.1 s (w8, 26), 3.7 s (w8_occ4, 4), 3.8 s (w8_occ0, 8), 4.3 s (shortk, 36): 26 s for the six
 NORM_CHILD_TIMEOUT = 180    # seconds for tools/norm_route_check.py; measured on the MI355X: 12 s for the whole child (8.8 s of cases and sweep)
 
 
@@ -55,7 +60,7 @@ def compiled_instantiations(tmpdir):
     from anyedit_amd import build as B
     hipcc = B._hipcc()
     keys = []
-    for src in ("gemm_conv.hip", "attention_fast.hip", "norm.hip", "gemm_rowpanel.hip", "ff_fused.hip"):
+    for src in ("gemm_conv.hip", "attention_fast.hip", "norm.hip", "gemm_rowpanel.hip", "ff_fused.hip", "attention.hip"):
         flags = [("-O0" if f == "-O3" else f) for f in B.FLAGS if f != "-fPIC"] + B.EXTRA.get(src, [])
         out = os.path.join(str(tmpdir), src.replace(".hip", ".ll"))
         subprocess.run([hipcc] + flags + ["--cuda-device-only", "-emit-llvm", "-S", os.path.join(B.CSRC, src), "-o", out], check=True,
@@ -103,12 +108,50 @@ def test_norm_ledger_rows_are_well_formed():
             assert any(byid[c]["C1"] and byid[c]["C1"] % (gp * byid[c]["C"] // byid[c]["groups"]) for c in what), f"{key}: no case with a concat split inside a pack"
 
 
+def test_attn_general_ledger_rows_are_well_formed():
+    ids = set(RC.ATTN_GENERAL_CASE_IDS)
+    others = set(RC.CASE_IDS) | set(RC.NORM_CASE_IDS) | set(RC.ROWPANEL_CASE_IDS)
+    assert len(ids) == len(RC.ATTN_GENERAL_CASES) and not ids & others, "duplicate case ids"
+    assert not set(RC.ATTN_GENERAL_LEDGER) & (set(RC.LEDGER) | set(RC.NORM_LEDGER) | set(RC.ROWPANEL_LEDGER))
+    # only this ledger has `env` rows: every row of the others is reached with no AE_* variable set
+    for led in (RC.LEDGER, RC.NORM_LEDGER, RC.ROWPANEL_LEDGER):
+        assert all(len(row) == 2 and row[0] == "default" for row in led.values())
+    byid = {c["id"]: c for c in RC.ATTN_GENERAL_CASES}
+    knobs = ("AE_ATTN_FAST", "AE_ATTN_W8", "AE_ATTN_SHORTK_QF1", "AE_ATTN_QF40", "AE_ATTN_SAM_OCC")
+    assert RC.ATTN_GENERAL_ENVS["default"] == {} and all(set(e) <= set(knobs) for e in RC.ATTN_GENERAL_ENVS.values())
+    for key, row in RC.ATTN_GENERAL_LEDGER.items():
+        assert re.fullmatch(r"attn_kernel<\d+, [124], [48], (true|false), [012], (true|false), (true|false), (true|false)>", key), key
+        assert (row[0] == "default" and len(row) == 2) or (row[0] == "env" and len(row) == 3 and row[1] and row[1] in RC.ATTN_GENERAL_ENVS.values()), (key, row)
+        what = row[-1]
+        assert what and all(c in ids for c in what), (key, [c for c in what if c not in ids])
+        # a case runs in the environment of the row that lists it, and the row is the instantiation the case declares
+        want_env = {} if row[0] == "default" else row[1]
+        assert all(RC.ATTN_GENERAL_ENVS[byid[c]["env"]] == want_env and RC.attn_general_key(byid[c]) == key for c in what), key
+        # every row is reached by at least one case whose last query block (QB = 16 QF NW rows) is ragged
+        assert any(byid[c]["Nq"] % (16 * byid[c]["qf"] * byid[c]["nw"]) for c in what), f"{key}: reached only at whole query blocks"
+        # every masked row: by a random mask and by a case with a wholly dead 64-key tile
+        if key.split(", ")[5] == "true":
+            assert any(byid[c]["mask"] == "rand" for c in what), f"{key}: no random mask"
+            assert any(byid[c]["mask"] in ("lead", "trail", "all") for c in what), f"{key}: no case with a wholly dead key tile"
+        # every rel-pos row: by a grid with kH != kW
+        if key.split(", ")[4] != "0":
+            assert any(byid[c]["rel"][0] != byid[c]["rel"][1] for c in what), f"{key}: no grid with kH != kW"
+    listed = {c for row in RC.ATTN_GENERAL_LEDGER.values() for c in row[-1]}
+    assert not ids - listed, f"cases that assert no route: {sorted(ids - listed)}"
+    for c in RC.ATTN_GENERAL_CASES:
+        assert c["op"] == "attn" and c["lay"] in ("qkv", "bhnd") and c.get("mask") in (None, "rand", "lead", "trail", "tailkey", "all"), c
+        assert c["B"] == 2 and c["B"] * c["H"] <= 6 and (c["Nq"] * c["Nk"] <= 512 * 512 or c["qf"] == 4), c
+        assert not c.get("rel") or c["rel"][0] * c["rel"][1] == c["Nk"], c
+        assert c.get("mask") != "tailkey" or c["Nk"] % 64, c
+        assert c.get("mask") not in ("lead", "trail") or c["Nk"] > 64, c
+
+
 def test_ledger_equals_the_compiled_instantiations(tmp_path):
     keys = compiled_instantiations(tmp_path)
     assert len(keys) == len(set(keys)), "a kernel key appears twice"
-    ledger = set(RC.LEDGER) | set(RC.NORM_LEDGER) | set(RC.ROWPANEL_LEDGER)
+    ledger = set(RC.LEDGER) | set(RC.NORM_LEDGER) | set(RC.ROWPANEL_LEDGER) | set(RC.ATTN_GENERAL_LEDGER)
     # (equality with the ledger's own count per family: a regular expression that silently finds nothing cannot pass)
-    for family in ("gemm_kernel<", "attn_") + tuple(f + "<" for f in NORM_FAMILIES + ROWPANEL_FAMILIES) + NORM_PLAIN:
+    for family in ("gemm_kernel<", "attn_fast_kernel<", "attn_pipe_kernel<", "attn_kernel<") + tuple(f + "<" for f in NORM_FAMILIES + ROWPANEL_FAMILIES) + NORM_PLAIN:
         assert sum(k.startswith(family) for k in keys) == sum(k.startswith(family) for k in ledger) > 0, (family, keys)
     compiled = set(keys)
     assert not compiled - ledger, f"instantiations without a ledger row (classify them in tests/route_cases.py): {sorted(compiled - ledger)}"
@@ -201,3 +244,38 @@ def test_rowpanel_route_cases_on_gpu():
     print("worst error / bound per case: " + ", ".join(f"{i} {r['ratio']:.3f}" for i, r in results.items()))
     print("worst error / bound per instantiation: " + ", ".join(
         f"{k} {max(results[c]['ratio'] for c in cases):.3f}" for k, (kind, cases) in RC.ROWPANEL_LEDGER.items()))
+
+
+def _attn_general_child(env_name):
+    env = {k: v for k, v in os.environ.items() if not k.startswith("AE_")}
+    env.update(RC.ATTN_GENERAL_ENVS[env_name])
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "attn_general_route_check.py"), "--env", env_name], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=ATTN_GENERAL_CHILD_TIMEOUT)
+    print(p.stdout)
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("ATTN_GENERAL_SUMMARY ")]
+    assert lines, f"attn_general_route_check.py --env {env_name} ended without a summary (exit {p.returncode}):\n{p.stdout[-4000:]}\n{p.stderr[-4000:]}"
+    summary = json.loads(lines[-1][len("ATTN_GENERAL_SUMMARY "):])
+    assert summary["aborted"] is None, f"GPU work stopped at {summary['aborted']}"
+    assert p.returncode in (0, 1), p.stderr[-4000:]
+    return summary["results"]
+
+
+@pytest.mark.gpu
+def test_attn_general_route_cases_on_gpu():
+    """attention.hip: every case reaches its ledger rows in its row's environment, leaves its guards and pad columns untouched, repeats bit for
+    bit, leaves no sentinel in out / lse / lse2 and passes the element-wise float64 checks on every row of every (batch, head); prints the worst
+    error / bound (output, log-sum-exp) per instantiation.  One child per environment, one after another: a child that faults, aborts or runs out
+    of time fails the test there (no summary line, a non-zero exit, or subprocess.TimeoutExpired) and the remaining children are not started."""
+    results = {}
+    for env_name in RC.ATTN_GENERAL_ENVS:
+        results.update({r["id"]: r for r in _attn_general_child(env_name)})
+    assert set(results) == set(RC.ATTN_GENERAL_CASE_IDS), sorted(set(RC.ATTN_GENERAL_CASE_IDS) ^ set(results))
+    failed = {i: r["error"] for i, r in results.items() if not r["ok"]}
+    assert not failed, failed
+    unreached = [(k, c) for k, row in RC.ATTN_GENERAL_LEDGER.items() for c in row[-1] if k not in results[c]["keys"]]
+    assert not unreached, unreached
+    assert all(r["guards"] == "intact" and isinstance(r["ratio"], float) and r["ratio"] <= 1.0 and isinstance(r["lse_ratio"], float)
+               and r["lse_ratio"] <= 1.0 for r in results.values())
+    print("worst error / bound per instantiation (output, log-sum-exp): " + ", ".join(
+        f"{k} {max(results[c]['ratio'] for c in row[-1]):.3f} {max(results[c]['lse_ratio'] for c in row[-1]):.3f}"
+        for k, row in RC.ATTN_GENERAL_LEDGER.items()))

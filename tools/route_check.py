@@ -382,6 +382,46 @@ def run_gemm(c, ops, gen, ln=False):
                 plan=lambda: ops.gemm_plan(M, N, K, epi, a2k or 0, f32, cs, 2 if ln else 1 if rs else 0))
 
 
+LOG2E = 1.4426950408889634
+
+
+def attn_segment_ref(qq, K, V, scale, bias=None, live=None):
+    """float64 reference of one attention segment of one (batch, head): qq [n, D] query rows, K / V [Nk, D]; bias = (rel_h [n, kH], rel_w [n, kW])
+    of the same rows; live = bool [Nk], False = a key the mask removes (masked_fill(-finfo.max) before the softmax, so a row with no live key is
+    the plain mean of the value rows).  Returns r = softmax(S) V, sv = softmax(S) |V|, bmax = max|rel_h| + max|rel_w| per row (None without a
+    bias), and L2 / L2_bnd: the log2-domain log-sum-exp over the live keys and its bound (module docstring; None when no key is live)."""
+    S = (qq @ K.t()) * scale
+    qk_abs = qq.abs() @ K.abs().t()
+    bmax = None
+    if bias is not None:
+        rh, rw = bias
+        S = S + rh.repeat_interleave(rw.shape[1], 1) + rw.repeat(1, rh.shape[1])
+        bmax = (rh.abs().max(1).values + rw.abs().max(1).values)[:, None]
+    Sl = S
+    if live is not None:
+        Sl, qk_abs = S[:, live], qk_abs[:, live]
+        S = S.masked_fill(~live[None, :], -torch.finfo(S.dtype).max)
+    L2 = lb = None
+    if Sl.shape[1]:
+        L2 = torch.logsumexp(Sl, -1) * LOG2E
+        per_logit = 2.0 ** -8 + (A_ACC + 2.0 ** -9) * scale * qk_abs.max(1).values
+        if bmax is not None:
+            per_logit = per_logit + 2.0 ** -9 * bmax[:, 0]
+        lb = LOG2E * per_logit + 2.0 ** -22 * L2.abs() + 1e-6
+    p = torch.softmax(S, -1)
+    return dict(r=p @ V, sv=p @ V.abs(), bmax=bmax, L2=L2, L2_bnd=lb)
+
+
+def attn_out_bound(r, sv, bmax=None, stored=None, gate=1.0):
+    """bound of the bf16 attention output: one rounding of the stored value (r, or `stored` = prev + gate r under accumulate / out_scale) and one
+    of each probability; with a rel-pos bias each logit may be off by 2^-9 (|rel_h| + |rel_w|) (BIAS 3 of attention_fast.hip: bf16 bias operands)"""
+    g = abs(gate)
+    bnd = 2.0 ** -8 * (r if stored is None else stored).abs() + g * 2.0 ** -8 * sv
+    if bmax is not None:
+        bnd = bnd + g * 2.0 ** -9 * bmax * (sv + r.abs())
+    return bnd + 1e-30
+
+
 def run_attn(c, ops, gen):
     B, H, Nq, Nk, D = c["B"], c["H"], c["Nq"], c["Nk"], c["D"]
     C = H * D
@@ -444,44 +484,24 @@ def run_attn(c, ops, gen):
                     (int(torch.randint(0, B, (1,), generator=gen)), int(torch.randint(0, H, (1,), generator=gen)))})
     refs, bnds = [], []
     lrefs, lbnds = [[], []], [[], []]     # log-sum-exp per segment (see "Bound, log-sum-exp" in the module docstring)
-    LOG2E = 1.4426950408889634
-
-    def lse_ref(S, qk_abs, bias_max=None):
-        L2 = torch.logsumexp(S, -1) * LOG2E
-        per_logit = 2.0 ** -8 + (A_ACC + 2.0 ** -9) * scale * qk_abs.max(1).values
-        if bias_max is not None:
-            per_logit = per_logit + 2.0 ** -9 * bias_max
-        return L2, LOG2E * per_logit + 2.0 ** -22 * L2.abs() + 1e-6
-
     for bb, hh in pairs:
         qq = Q4[bb, hh, qsel]
-        S = (qq @ K4[bb, hh].t()) * scale
-        if rel:
-            kH, kW = rel
-            bh = bb * H + hh
-            S = S + relh[bh, qsel].to(F64).repeat_interleave(kW, 1) + relw[bh, qsel].to(F64).repeat(1, kH)
-            bmax = (relh[bh, qsel].abs().to(F64).max(1).values + relw[bh, qsel].abs().to(F64).max(1).values)[:, None]
-        L2, lb = lse_ref(S, qq.abs() @ K4[bb, hh].abs().t(), bmax[:, 0] if rel else None)
-        lrefs[0].append(L2)
-        lbnds[0].append(lb)
-        p = torch.softmax(S, -1)
-        r = p @ V4[bb, hh]
-        sv = p @ V4[bb, hh].abs()
+        bh = bb * H + hh
+        bias = (relh[bh, qsel].to(F64), relw[bh, qsel].to(F64)) if rel else None
+        s1 = attn_segment_ref(qq, K4[bb, hh], V4[bb, hh], scale, bias=bias)
+        lrefs[0].append(s1["L2"])
+        lbnds[0].append(s1["L2_bnd"])
+        r, sv = s1["r"], s1["sv"]
         if nk2:
             K2 = k2.as_strided((B, H, nk2, D), st2 + (1,), 0).to(F64)
             V2 = k2.as_strided((B, H, nk2, D), st2 + (1,), C).to(F64)
-            S2 = (qq @ K2[bb, hh].t()) * scale
-            L2, lb = lse_ref(S2, qq.abs() @ K2[bb, hh].abs().t())
-            lrefs[1].append(L2)
-            lbnds[1].append(lb)
-            p2 = torch.softmax(S2, -1)
-            r = r + float(s2[bb]) * (p2 @ V2[bb, hh])
-            sv = sv + float(s2[bb]) * (p2 @ V2[bb, hh].abs())
-        bnd = 2.0 ** -8 * r.abs() + 2.0 ** -8 * sv
-        if rel:   # the bias may enter the logit MFMA chain as bf16 operands (BIAS 3): each logit off by <= 2^-9 (|rel_h| + |rel_w|)
-            bnd = bnd + 2.0 ** -9 * bmax * (sv + r.abs())
+            seg2 = attn_segment_ref(qq, K2[bb, hh], V2[bb, hh], scale)
+            lrefs[1].append(seg2["L2"])
+            lbnds[1].append(seg2["L2_bnd"])
+            r = r + float(s2[bb]) * seg2["r"]
+            sv = sv + float(s2[bb]) * seg2["sv"]
         refs.append(r)
-        bnds.append(bnd + 1e-30)
+        bnds.append(attn_out_bound(r, sv, s1["bmax"]))
 
     def gather(o):
         ov = o.view.reshape(B, Nq, H, D).cpu()
