@@ -71,7 +71,9 @@ __device__ __forceinline__ Fp8Scales fp8_scales(const float* amax, float scale) 
     Fp8Scales s;
     const float sk = ak / F8_MAX;                       // K8 = k / sk
     const float qprime = aq * scale * F8_LOG2E * sk;    // amax of q * (scale log2e sk)
-    const float sig = pow2_ceil(qprime / F8_MAX);       // Q8 = q' / 2^e_q
+    // Q8 = q' / 2^e_q.  Floored at the smallest normal: with q AND k of a head all-zero q' / 448 underflows to 0, and sig = 0 made qmul
+    // infinite and Q8 = 0 * inf = NaN (the whole head's output NaN instead of the mean of v)
+    const float sig = pow2_ceil(fmaxf(qprime / F8_MAX, 1.17549435e-38f));
     s.kmul = 1.0f / sk;
     s.qmul = scale * F8_LOG2E * sk / sig;
     s.e_q = (int)((__float_as_uint(sig) >> 23) & 0xFF) - 127;
