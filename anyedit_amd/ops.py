@@ -2219,6 +2219,24 @@ def gaussian_moments(moments, noise=None, want_stats=False):
     return (z, *stats) if want_stats else z
 
 
+def _msda_shapes(name, value, spatial_shapes, level_start_index, sampling_locations, attention_weights):
+    """Host-side shape comparisons only (no device read, so they hold under graph capture): the C entry sees raw pointers, and a
+    mismatch would make the kernel read past a tensor.  -> (bs, S, heads, d, Q, L, P)"""
+    bs, S, heads, d = value.shape
+    if sampling_locations.dim() != 6 or sampling_locations.shape[-1] != 2:
+        raise ValueError(f"{name}: sampling_locations must be [bs, Q, heads, L, P, 2], got {tuple(sampling_locations.shape)}")
+    lb, Q, lh, L, P, _ = sampling_locations.shape
+    if lb != bs or lh != heads:
+        raise ValueError(f"{name}: sampling_locations {tuple(sampling_locations.shape)} are not of value's bs={bs}, heads={heads}")
+    if tuple(attention_weights.shape) != (bs, Q, heads, L, P):
+        raise ValueError(f"{name}: attention_weights {tuple(attention_weights.shape)} != {(bs, Q, heads, L, P)}")
+    if tuple(spatial_shapes.shape) != (L, 2):
+        raise ValueError(f"{name}: spatial_shapes {tuple(spatial_shapes.shape)} != {(L, 2)}")
+    if tuple(level_start_index.shape) != (L,):
+        raise ValueError(f"{name}: level_start_index {tuple(level_start_index.shape)} != {(L,)}")
+    return bs, S, heads, d, Q, L, P
+
+
 def ms_deform_attn(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step=None, validated=False):
     """Drop-in for `_C.ms_deform_attn_forward` (GroundingDINO ms_deform_attn.py:42-60): value [bs, S, heads, d], spatial_shapes
     [L, 2] int64, level_start_index [L] int64, sampling_locations [bs, Q, heads, L, P, 2], attention_weights [bs, Q, heads, L, P]
@@ -2226,8 +2244,7 @@ def ms_deform_attn(value, spatial_shapes, level_start_index, sampling_locations,
     `validated=True`: the caller has checked on the host that the levels add up to S (the check here reads the device tensor back, a
     synchronisation no graph capture allows)."""
     _chk(value, torch.float32, "ms_deform_attn.value", 4)
-    bs, S, heads, d = value.shape
-    _, Q, _, L, P, _ = sampling_locations.shape
+    bs, S, heads, d, Q, L, P = _msda_shapes("ms_deform_attn", value, spatial_shapes, level_start_index, sampling_locations, attention_weights)
     value = value.contiguous()
     loc = sampling_locations.float().contiguous()
     w = attention_weights.float().contiguous()
@@ -2245,8 +2262,8 @@ def ms_deform_attn_bwd(value, spatial_shapes, level_start_index, sampling_locati
     """Drop-in for `_C.ms_deform_attn_backward` (GroundingDINO ms_deform_attn.py:68-90): returns (grad_value [bs, S, heads, d],
     grad_sampling_loc [bs, Q, heads, L, P, 2], grad_attn_weight [bs, Q, heads, L, P]), fp32."""
     _chk(value, torch.float32, "ms_deform_attn_bwd.value", 4)
-    bs, S, heads, d = value.shape
-    _, Q, _, L, P, _ = sampling_locations.shape
+    bs, S, heads, d, Q, L, P = _msda_shapes("ms_deform_attn_bwd", value, spatial_shapes, level_start_index, sampling_locations,
+                                            attention_weights)
     value = value.contiguous()
     loc = sampling_locations.float().contiguous()
     w = attention_weights.float().contiguous()
