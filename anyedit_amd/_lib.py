@@ -161,6 +161,9 @@ SIGNATURES = {
     "ae_ppm_pool_rows_bf16": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
     "ae_resize_concat_rows_bf16": [c_void_p] * 8 + [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_void_p],
     "ae_seg_argmax_u8": [c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p],
+    "ae_attn_mutual_bf16": [c_void_p] * 4 + [c_int] * 4 + [c_long] * 12 + [c_float, ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p],
+    "ae_attn_token_map_bf16": [c_void_p] * 3 + [c_int] * 5 + [c_long] * 6 + [c_float, ctypes.POINTER(ctypes.c_ulonglong), c_int, c_void_p],
+    "ae_masactrl_classes": [c_void_p, c_long, c_int, c_int, c_float, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p],
 }
 _RESTYPES = {"ae_last_error": ctypes.c_char_p, "ae_groupnorm_workspace_floats": c_long, "ae_conv3x3_workspace_floats": c_long,
              "ae_groupnorm_bwd_workspace_floats": c_long, "ae_attn_fp8_workspace_bytes": c_long, "ae_attn_bwd_workspace_floats": c_long,

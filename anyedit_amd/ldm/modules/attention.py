@@ -204,10 +204,16 @@ class CrossAttention(nn.Module):
             g, be = norm._affine()
             return ops.ln_gemm(x, g, be, norm.eps, pk[wname])
 
+        # MasaCtrl (anyedit_amd.masactrl): a registered editor replaces the attention core only; with none set the launches are today's
+        editor = self.__dict__.get("editor")
         if context_rows is None and kv is None:
             qkv = proj("qkv")  # [B*N, 3*inner]
             s = (N * 3 * inner, d, 3 * inner)
-            o = ops.attention(qkv, qkv[:, inner:], qkv[:, 2 * inner:], B, h, N, N, d, self.scale, s, s, s, key_mask=key_mask)
+            if editor is not None:
+                o = editor(self, False, B, N, lambda: ops.attention(qkv, qkv[:, inner:], qkv[:, 2 * inner:], B, h, N, N, d, self.scale, s, s, s,
+                                                                    key_mask=key_mask), qkv=qkv)
+            else:
+                o = ops.attention(qkv, qkv[:, inner:], qkv[:, 2 * inner:], B, h, N, N, d, self.scale, s, s, s, key_mask=key_mask)
         else:
             q = proj("q")
             if kv is None:
@@ -215,15 +221,16 @@ class CrossAttention(nn.Module):
             Nk = kv.shape[0] // B
             qs = (N * inner, d, inner)
             ks = (Nk * 2 * inner, d, 2 * inner)
-            if adapter is not None and (d <= 96 or (d == 160 and _SEG2_160)) and key_mask is None:
-                # both softmaxes in ONE launch: Q read once, O written once (the 4-token expert segment used to cost as much
-                # as the 77-token text segment because it re-read Q and read-modify-wrote O)
-                kv_ip, gate = adapter
-                T_ip = kv_ip.shape[0] // B
-                ks_ip = (T_ip * 2 * inner, d, 2 * inner)
-                seg2 = (kv_ip, kv_ip[:, inner:], T_ip, ks_ip, ks_ip, gate)
-                o = ops.attention(q, kv, kv[:, inner:], B, h, N, Nk, d, self.scale, qs, ks, ks, seg2=seg2)
-            else:
+
+            def core():
+                if adapter is not None and (d <= 96 or (d == 160 and _SEG2_160)) and key_mask is None:
+                    # both softmaxes in ONE launch: Q read once, O written once (the 4-token expert segment used to cost as much
+                    # as the 77-token text segment because it re-read Q and read-modify-wrote O)
+                    kv_ip, gate = adapter
+                    T_ip = kv_ip.shape[0] // B
+                    ks_ip = (T_ip * 2 * inner, d, 2 * inner)
+                    seg2 = (kv_ip, kv_ip[:, inner:], T_ip, ks_ip, ks_ip, gate)
+                    return ops.attention(q, kv, kv[:, inner:], B, h, N, Nk, d, self.scale, qs, ks, ks, seg2=seg2)
                 o = ops.attention(q, kv, kv[:, inner:], B, h, N, Nk, d, self.scale, qs, ks, ks, key_mask=key_mask)
                 if adapter is not None:
                     kv_ip, gate = adapter
@@ -231,6 +238,9 @@ class CrossAttention(nn.Module):
                     ks_ip = (T_ip * 2 * inner, d, 2 * inner)
                     ops.attention(q, kv_ip, kv_ip[:, inner:], B, h, N, T_ip, d, self.scale, qs, ks_ip, ks_ip, out=o,
                                   out_scale=gate, accumulate=True)
+                return o
+
+            o = core() if editor is None else editor(self, True, B, N, core, q=q, kv=kv, Nk=Nk)
         return self.to_out[0].rows(o.reshape(B * N, inner), residual=residual, rowstats=out_rowstats)
 
     def forward(self, x, context=None, mask=None):

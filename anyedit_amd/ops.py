@@ -1901,6 +1901,114 @@ def seg_argmax(logits, ncls, B, h, w, mid, out_size=None, palette=None, labels=N
     return labels if palette is None else (labels, colours)
 
 
+# --------------------------------------------------------------------------- MasaCtrl mutual self-attention (csrc/masactrl.hip)
+MUTUAL_HEAD_DIMS = (40, 64, 80, 160)
+MUTUAL_MAX_BATCH = 64
+TOKEN_MAP_MAX_KEYS, TOKEN_MAP_MAX_DIM = 128, 160
+MASACTRL_MAX_PAIRS = 8
+CLS_ANY = 255
+
+
+def _cls_buf(t, name, B, N):
+    _chk(t, torch.uint8, name, 2)
+    if tuple(t.shape) != (B, N) or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous uint8 [{B}, {N}] tensor, got {tuple(t.shape)}")
+
+
+def attention_mutual(q, k, v, B, H, N, D, scale, q_strides, k_strides, v_strides, src, qcls=None, kcls=None, kcnt=None, out=None, o_strides=None):
+    """Self-attention in which sample b's queries read the keys / values of sample src[b] (ae_attn_mutual_bf16).  q/k/v: bf16 tensors addressed via
+    (batch, head, row) element strides, as `attention` takes them; src: B host ints.  qcls uint8 [B, N] (255 = any key), kcls uint8 [B, N] and kcnt int32
+    [B, 2] (class counts per sample, as `masactrl_classes` writes them; both indexed by src[b]): key j is allowed for query (b, i) iff qcls is None, or
+    qcls[b, i] == 255, or kcls[src[b], j] == qcls[b, i]; a query whose class has no key in its source gets the mean of V.  out: [B, N, H*D] bf16."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _chk(t, BF16, "attention_mutual." + n)
+    if D not in MUTUAL_HEAD_DIMS:
+        raise ValueError(f"attention_mutual: head dims {MUTUAL_HEAD_DIMS} are covered, got {D}")
+    src = tuple(int(s) for s in src)
+    if len(src) != B or B < 1 or B > MUTUAL_MAX_BATCH or any(s < 0 or s >= B for s in src):
+        raise ValueError(f"attention_mutual: src needs {B} sample indices in [0, {B}) (B <= {MUTUAL_MAX_BATCH}), got {src}")
+    if N < 1 or H < 1:
+        raise ValueError(f"attention_mutual: bad sizes H={H} N={N}")
+    if qcls is not None:
+        if kcls is None or kcnt is None:
+            raise ValueError("attention_mutual: qcls needs kcls and kcnt")
+        _cls_buf(qcls, "attention_mutual.qcls", B, N)
+        _cls_buf(kcls, "attention_mutual.kcls", B, N)
+        _chk(kcnt, torch.int32, "attention_mutual.kcnt", 2)
+        if tuple(kcnt.shape) != (B, 2) or not kcnt.is_contiguous():
+            raise ValueError(f"attention_mutual.kcnt: expected a contiguous int32 [{B}, 2] tensor, got {tuple(kcnt.shape)}")
+    elif kcls is not None or kcnt is not None:
+        raise ValueError("attention_mutual: kcls / kcnt without qcls")
+    if out is None:
+        out = torch.empty(B, N, H * D, dtype=BF16, device=q.device)
+    else:
+        _chk(out, BF16, "attention_mutual.out")
+    if o_strides is None:
+        o_strides = (N * H * D, D, H * D)
+    arr = (ctypes.c_int * B)(*src)
+    check(lib.ae_attn_mutual_bf16(_p(q), _p(k), _p(v), _p(out), B, H, N, D, *q_strides, *k_strides, *v_strides, *o_strides, float(scale), arr,
+                                  _p(qcls), _p(kcls), _p(kcnt), _s()), "ae_attn_mutual_bf16")
+    return out
+
+
+def token_set_words(tokens):
+    """(low, high) uint64 words of a token set: bit j set iff token j (0 .. 127) is in `tokens`"""
+    lo = hi = 0
+    for t in tokens:
+        t = int(t)
+        if not 0 <= t < TOKEN_MAP_MAX_KEYS:
+            raise ValueError(f"token set: token indices 0 .. {TOKEN_MAP_MAX_KEYS - 1} are covered, got {t}")
+        if t < 64:
+            lo |= 1 << t
+        else:
+            hi |= 1 << (t - 64)
+    return lo, hi
+
+
+def attention_token_map(q, k, B, H, N, Nk, D, scale, q_strides, k_strides, token_sets, out=None, accumulate=False):
+    """Head-averaged softmax probabilities of a short-key attention summed over a per-sample token set (ae_attn_token_map_bf16):
+    out[b, i] (+)= 1/H sum_h sum_{j in token_sets[b]} softmax_j(scale q[b,h,i] . k[b,h,j]); out fp32 [B, N].  q / k: bf16 tensors read in place through
+    (batch, head, row) element strides; token_sets: B iterables of token indices below Nk (<= 128).  accumulate: add to `out` (which must be given)."""
+    _chk(q, BF16, "attention_token_map.q")
+    _chk(k, BF16, "attention_token_map.k")
+    if Nk < 1 or Nk > TOKEN_MAP_MAX_KEYS or D % 8 or not 0 < D <= TOKEN_MAP_MAX_DIM or not 1 <= B <= MUTUAL_MAX_BATCH or N < 1 or H < 1:
+        raise ValueError(f"attention_token_map: Nk <= {TOKEN_MAP_MAX_KEYS}, head dims that are multiples of 8 up to {TOKEN_MAP_MAX_DIM} and B <= "
+                         f"{MUTUAL_MAX_BATCH} are covered, got B={B} H={H} N={N} Nk={Nk} D={D}")
+    token_sets = [tuple(int(t) for t in s) for s in token_sets]
+    if len(token_sets) != B or any(t >= Nk for s in token_sets for t in s):
+        raise ValueError(f"attention_token_map: need {B} token sets with indices below Nk={Nk}, got {token_sets}")
+    if accumulate and out is None:
+        raise ValueError("attention_token_map: accumulate needs the buffer to add to")
+    out = _out_buf(out, torch.float32, (B, N), "attention_token_map.out", q.device)
+    words = [w for s in token_sets for w in token_set_words(s)]
+    arr = (ctypes.c_ulonglong * (2 * B))(*words)
+    check(lib.ae_attn_token_map_bf16(_p(q), _p(k), _p(out), B, H, N, Nk, D, *q_strides, *k_strides, float(scale), arr, 1 if accumulate else 0, _s()),
+          "ae_attn_token_map_bf16")
+    return out
+
+
+def masactrl_classes(maps, S, R, thres, pairs, cls, counts):
+    """Min-max normalisation, nearest resize S x S -> R x R (F.interpolate's index rule) and `>= thres` of several maps in one launch, without a
+    read-back (ae_masactrl_classes).  maps: fp32 [B, S*S] contiguous; pairs: [(sample, out_row), ...] (1 .. 8); cls: uint8 [rows, R*R] and counts: int32
+    [rows, 2] (zeros, ones per written row), both contiguous.  A constant map gives all-zero classes.  Returns (cls, counts)."""
+    _chk(maps, torch.float32, "masactrl_classes.maps", 2)
+    if S < 1 or R < 1 or maps.shape[1] != S * S or not maps.is_contiguous():
+        raise ValueError(f"masactrl_classes.maps: expected contiguous fp32 [B, {S * S}] maps, got {tuple(maps.shape)}")
+    pairs = [(int(s), int(o)) for s, o in pairs]
+    _chk(cls, torch.uint8, "masactrl_classes.cls", 2)
+    _chk(counts, torch.int32, "masactrl_classes.counts", 2)
+    rows = cls.shape[0]
+    if cls.shape[1] != R * R or not cls.is_contiguous() or tuple(counts.shape) != (rows, 2) or not counts.is_contiguous():
+        raise ValueError(f"masactrl_classes: cls must be contiguous uint8 [rows, {R * R}] and counts int32 [rows, 2], got {tuple(cls.shape)} and "
+                         f"{tuple(counts.shape)}")
+    if not 1 <= len(pairs) <= MASACTRL_MAX_PAIRS or any(not 0 <= s < maps.shape[0] or not 0 <= o < rows for s, o in pairs):
+        raise ValueError(f"masactrl_classes: 1 .. {MASACTRL_MAX_PAIRS} (sample, out_row) pairs inside the buffers are covered, got {pairs}")
+    sa = (ctypes.c_int * len(pairs))(*(s for s, _ in pairs))
+    oa = (ctypes.c_int * len(pairs))(*(o for _, o in pairs))
+    check(lib.ae_masactrl_classes(_p(maps), maps.stride(0), S, R, float(thres), len(pairs), sa, oa, _p(cls), _p(counts), _s()), "ae_masactrl_classes")
+    return cls, counts
+
+
 def rows_to_nchw_out(x, out):
     """channels-last bf16 rows [B*H*W, C] contiguous -> the given [B, C, H, W] buffer (fp32 or bf16, contiguous): `rows_to_nchw` into a
     buffer the caller owns (no allocation)."""

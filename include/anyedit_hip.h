@@ -725,6 +725,39 @@ int ae_resize_concat_rows_bf16(const void* const* src, const int* src_h, const i
 int ae_seg_argmax_u8(const float* logits, long ld, int ncls, const void* palette, void* labels, void* colours, int B, int h, int w, int Hm, int Wm, int Ho,
                      int Wo, void* stream);
 
+/* ---- MasaCtrl, mutual self-attention control (csrc/masactrl.hip; AnyEdit_Collection/other_modules/masactrl/masactrl.py, registered on the UNet by
+ * masactrl_utils.py::regiter_attention_editor_ldm).  The reference hook is handed sim and attn ([B h, N, N]) of every attention call; these entry points
+ * never form them.  No atomics, fixed summation orders (a second call is bit-identical), current stream only, no host synchronisation, no allocation.
+ * ae_attn_mutual_bf16: masactrl.py:41-72 (attn_batch / forward: the target's queries on the source's keys and values), :138-193 (mask-guided: sim_fg /
+ *   sim_bg = sim + finfo.min on the other class, two softmaxes, the blend by the target mask) and :231-258, :285-334 (the same with generated masks).
+ *   Self-attention in which sample b's queries read the keys and values of sample src[b]: out[b] = softmax_j(scale q_b . k_src[b],j) v_src[b],j.
+ *   q / k / v bf16 addressed in place through (batch, head, row) element strides as ae_attn_fwd_bf16 takes them (rows 16-byte aligned), out bf16 through
+ *   o-strides (multiples of 4); src: B host ints in [0, B), read during the call (B <= 64).  Classes (optional): qcls uint8 [B, N] or NULL, kcls uint8
+ *   [B, N] and kcnt int32 [B, 2] (both indexed by src[b]; kcnt[s][c] = number of keys of sample s with class c, as ae_masactrl_classes writes it).  Key j
+ *   is allowed for query (b, i) iff qcls is NULL, or qcls[b][i] == 255, or kcls[src[b]][j] == qcls[b][i]; classes are 0 / 1.  A query whose class has
+ *   no key in its source (kcnt == 0; also a class byte other than 0, 1, 255) gets the plain mean of V over all keys: the reference adds finfo.min to every
+ *   logit, which leaves them all equal in fp32.  One class-matched softmax per row replaces the reference's two softmaxes and its blend (the blend's mask
+ *   is 0 / 1, so it selects).  fp32 logits and softmax statistics, bf16 probabilities into the PV product, fp32 accumulation; a key tile with no allowed
+ *   key leaves a row's running maximum untouched (no NaN).  head_dim 40, 64, 80, 160 and any N >= 1; anything else: AE_ERR_UNSUPPORTED with a message.
+ * ae_attn_token_map_bf16: masactrl.py:277-280 (`attn.reshape(-1, heads, N, Nk).mean(1)` of a 16x16 cross-attention, kept per layer) with the token
+ *   selection of aggregate_cross_attn_map (:260-267: `attn_map[..., idx]`, summed over a list) taken at once:
+ *     out[b][i] (+)= (1 / H) sum_h sum_{j in set_b} softmax_j(scale q_{b,h,i} . k_{b,h,j}),   out fp32 [B, N] contiguous, accumulate != 0: added to out.
+ *   (The reference's mean over the collected layers is a positive factor that its min-max normalisation removes: summing the layers' maps is enough.)
+ *   q / k bf16 read in place through (batch, head, row) strides; Nk <= 128, head_dim a multiple of 8 up to 160, B <= 64; token_sets: 2 B host uint64,
+ *   bit j % 64 of word 2 b + j / 64 set iff token j belongs to sample b's set.  No PV product; the heads are added in order inside the launch.
+ * ae_masactrl_classes: aggregate_cross_attn_map's min-max normalisation (:268-270), F.interpolate(mode="nearest") to the self-attention's resolution
+ *   (:303, :315) and the in-place binarisation (:245-247, :321-323) of `npairs` (1 .. 8) maps in one launch, with no read-back.  Pair p reads the S x S
+ *   map maps[sample[p] * map_ld ..] (fp32) and writes cls[out_row[p]][R R] (uint8, 1 where (x - min) / (max - min) >= thres at the nearest source pixel
+ *   min(floor(dst * S / R), S - 1), fp32 as the reference) and counts[out_row[p]][2] (int32: zeros, ones).  sample / out_row: host arrays.  A constant
+ *   map is 0 / 0 = NaN in the reference (its mask then stays NaN); here it gives all-zero classes, i.e. counts (R R, 0).                            */
+int ae_attn_mutual_bf16(const void* q, const void* k, const void* v, void* out, int B, int H, int N, int D, long q_sb, long q_sh, long q_sn, long k_sb,
+                        long k_sh, long k_sn, long v_sb, long v_sh, long v_sn, long o_sb, long o_sh, long o_sn, float scale, const int* src,
+                        const unsigned char* qcls, const unsigned char* kcls, const int* kcnt, void* stream);
+int ae_attn_token_map_bf16(const void* q, const void* k, float* out, int B, int H, int N, int Nk, int D, long q_sb, long q_sh, long q_sn, long k_sb,
+                           long k_sh, long k_sn, float scale, const unsigned long long* token_sets, int accumulate, void* stream);
+int ae_masactrl_classes(const float* maps, long map_ld, int S, int R, float thres, int npairs, const int* sample, const int* out_row, unsigned char* cls,
+                        int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
