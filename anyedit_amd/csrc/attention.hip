@@ -17,22 +17,15 @@
 //     both operands -> no cross-lane traffic for P);
 //   * V is transposed while it is written to LDS (key index permuted so each lane's 8 contraction slots are one
 //     16-byte ds_read_b128);
-//   * head_dim is padded inside the kernel (40 -> 64 for QK^T, 48 for PV); q/k/v/out are addressed through
+//   * head_dim is padded inside the kernel (40 -> 48 for QK^T, 48 for PV; every tile constant comes from AttnTile, attn_tile.hpp); q/k/v/out are addressed through
 //     (batch, head, row) strides, so the 'b n (h d) -> (b h) n d' rearranges of the reference never happen;
 //   * softmax in fp32, exp2 domain; bf16 P (v_cvt_pk_bf16_f32); fp32 accumulation of O.
 #include "attention.hpp"
+#include "attn_tile.hpp"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
-
-constexpr int KT = 64;  // keys per tile
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float NEG_BIG = -1.0e30f;  // finite "masked" logit: behaves like masked_fill(-finfo.max) (attention.py:186-187)
-
-__device__ __forceinline__ int vt_pos(int key) {  // key = 16 f + 4 g + r  ->  16 g + 4 f + r
-    return ((key >> 2) & 3) * 16 + (key >> 4) * 4 + (key & 3);
-}
 
 // NW waves per block, QF 16-row query fragments per wave.  (NW=4,QF=2) and (NW=8,QF=1) cover the same 128 query rows per
 // block with the same LDS; the latter halves the per-wave register state (4 instead of 2 waves per SIMD -> the exp-bound
@@ -44,24 +37,10 @@ __device__ __forceinline__ int vt_pos(int key) {  // key = 16 f + 4 g + r  ->  1
 // VGPRs, i.e. ONE 8-wave block per CU; the cap costs 40-160 bytes of scratch per lane.
 template <int D, int QF, int NW, bool DBUF, int BIAS, bool HAS_MASK, bool SEG2 = false, bool OCC4 = false>
 __global__ __launch_bounds__(64 * NW, (D <= 96 ? ((NW == 8 && (BIAS == 0 || OCC4)) ? 4 : 2) : 1)) void attn_kernel(const AttnArgs p) {
-    constexpr bool HAS_BIAS = BIAS != 0;
-    constexpr int NT = 64 * NW;
-    constexpr int NC = D / 32;                 // full K=32 MFMAs per (key frag, q frag)
-    constexpr bool TAIL16 = (D % 32) != 0;     // head-dim remainder (8 or 16) goes through ONE K=16 MFMA instead of padding to 32
-    static_assert(D % 32 == 0 || D % 32 == 8 || D % 32 == 16, "head_dim % 32 must be 0, 8 or 16");
-    constexpr int DQK = NC * 32 + (TAIL16 ? 16 : 0);
-    constexpr int DV = (D + 15) / 16 * 16;
-    constexpr bool ONES = DV > D;  // a free padding row of V^T holds 1.0: the PV MFMA then also produces sum_k P[q][k] (the softmax
-                                   // denominator, rescaled together with O) and the 32 VALU adds per tile disappear
-    constexpr int NDF = DV / 16;   // 16-row fragments of O^T
-    constexpr int DCH = D / 8;     // 16-byte chunks per K/V row
-    constexpr int KROW = DQK + 8;  // LDS row strides (elements), +16 B pad
-    constexpr int VROW = KT + 8;
-    constexpr int KCH = (KT * DCH + NT - 1) / NT;
-    constexpr int VCH = ((KT / 2) * DCH + NT - 1) / NT;
-    constexpr int NBUF = DBUF ? 2 : 1;
-    constexpr int KSZ = KT * KROW, VSZ = DV * VROW;
-    static_assert(D % 8 == 0, "head_dim must be a multiple of 8");
+    using T = AttnTile<D, QF, NW, DBUF>;
+    constexpr bool HAS_BIAS = BIAS != 0, TAIL16 = T::TAIL16, ONES = T::ONES;
+    constexpr int NT = T::NT, NC = T::NC, DQK = T::DQK, DV = T::DV, NDF = T::NDF, DCH = T::DCH, KROW = T::KROW, VROW = T::VROW, KCH = T::KCH, VCH = T::VCH,
+                  NBUF = T::NBUF, KSZ = T::KSZ, VSZ = T::VSZ;
 
     __shared__ __attribute__((aligned(16))) bf16_t smem[NBUF * (KSZ + VSZ)];
     bf16_t* const sK = smem;
@@ -69,7 +48,7 @@ __global__ __launch_bounds__(64 * NW, (D <= 96 ? ((NW == 8 && (BIAS == 0 || OCC4
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, lg = lane >> 4;
-    constexpr int QB = NW * 16 * QF;  // query rows per block
+    constexpr int QB = T::QB;
     const int nqb = (p.Nq + QB - 1) / QB;
     const int vb = xcd_remap(blockIdx.x, nqb * p.B * p.H);
     const int bh = vb / nqb, qb = vb % nqb;
@@ -115,7 +94,7 @@ __global__ __launch_bounds__(64 * NW, (D <= 96 ? ((NW == 8 && (BIAS == 0 || OCC4
     // small key grids (SAM's 14x14 windows): the block's bias rows [query][kH + kW] are copied into LDS once — the per-key
     // lookups are index-dependent, and as global loads each one exposed a full memory round trip (3x the kernel time)
     constexpr int BIAS_LDS_W = 32;                 // kH, kW <= 32 each
-    constexpr int BQ = NW * 16 * QF;               // queries per block
+    constexpr int BQ = T::QB;                      // queries per block
     __shared__ float sBiasH[BIAS == 1 ? BQ * BIAS_LDS_W : 1];
     __shared__ float sBiasW[BIAS == 1 ? BQ * BIAS_LDS_W : 1];
     const bool bias_in_lds = BIAS == 1 && p.kH <= BIAS_LDS_W && p.kW <= BIAS_LDS_W;
@@ -238,17 +217,7 @@ __global__ __launch_bounds__(64 * NW, (D <= 96 ? ((NW == 8 && (BIAS == 0 || OCC4
     #pragma unroll
             for (int i = 0; i < VCH; ++i) {
                 if ((KT / 2) * DCH % NT == 0 || tid + i * NT < (KT / 2) * DCH) {
-                    const int pos = vt_pos(2 * v_pr[i]);  // even; key 2pr+1 lands at pos+1
-                    const uint32_t a0[4] = {rv[i][0].x, rv[i][0].y, rv[i][0].z, rv[i][0].w};
-                    const uint32_t a1[4] = {rv[i][1].x, rv[i][1].y, rv[i][1].z, rv[i][1].w};
-    #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        // d = c*8 + 2e (low halves) and c*8 + 2e + 1 (high halves)
-                        const uint32_t lo = __builtin_amdgcn_perm(a1[e], a0[e], 0x05040100u);  // {a0.lo16, a1.lo16}: one v_perm_b32
-                        const uint32_t hi = __builtin_amdgcn_perm(a1[e], a0[e], 0x07060302u);  // {a0.hi16, a1.hi16}
-                        *reinterpret_cast<uint32_t*>(dV + (v_c[i] * 8 + 2 * e) * VROW + pos) = lo;
-                        *reinterpret_cast<uint32_t*>(dV + (v_c[i] * 8 + 2 * e + 1) * VROW + pos) = hi;
-                    }
+                    store_vt_pair(dV, VROW, v_c[i], vt_pos(2 * v_pr[i]), rv[i][0], rv[i][1]);  // the position is even; key 2 pr + 1 lands beside it
                 }
             }
         };
@@ -484,8 +453,7 @@ inline int sam_occ() {
 // not compiled (tests/route_cases.py, ATTN_GENERAL_LEDGER: every instantiation here is one some environment reaches)
 template <int D, int QF, bool DBUF, int NW = 4, bool REL = true, bool SEG2K = true>
 int launch_attn(const AttnArgs& a, hipStream_t stream) {
-    constexpr int QB = NW * 16 * QF;
-    constexpr int NT = 64 * NW;
+    constexpr int QB = AttnTile<D, QF, NW, DBUF>::QB, NT = AttnTile<D, QF, NW, DBUF>::NT;
     const long blocks = (long)((a.Nq + QB - 1) / QB) * a.B * a.H;
     dim3 grid((unsigned)blocks), block(NT);
     if (a.rel_h && a.key_mask) { ae_set_error("ae_attn_fwd_bf16: rel-pos bias together with key_mask is not supported"); return AE_ERR_UNSUPPORTED; }

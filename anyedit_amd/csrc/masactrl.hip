@@ -9,22 +9,19 @@
 //             :300-303 / :312-323 resize and binarisation (ae_masactrl_classes).
 // The reference hook receives sim and attn ([B h, N, N]) of every attention call; none of them is formed here.
 //
-// ae_attn_mutual_bf16: the core of attention.hip's general kernel written anew for this file (no template of attention.hip /
-// attention_fast.hip changes): 4 waves x 2 query fragments, 64-key tiles through LDS, S^T = K Q^T with
+// ae_attn_mutual_bf16: the streaming 64-key-tile design of attention.hip's general kernel with the same tile constants (AttnTile, attn_tile.hpp) and
+// V^T placement (attn_layout.hpp); the kernel body is this file's own twin of attn_kernel's, kept equal to it bit for bit by tests/test_hip_masactrl.py: 4 waves x 2 query fragments, 64-key tiles through LDS, S^T = K Q^T with
 // v_mfma_f32_16x16x32_bf16, fp32 online softmax in the exp2 domain, bf16 P as the B operand of O^T = V^T P^T.  The class
 // bytes of a key tile ride through LDS beside K.  A disallowed logit is the finite -1e30; while a row has seen no allowed
 // key its running maximum stays -1e30 and the exponent offset is taken as 0, so its probabilities are exactly 0 (no NaN, no
 // exp2(0) = 1 for masked keys).  A row whose class has no key in its source (class count 0) has every logit replaced by 0:
 // the plain mean of V over all keys, what sim + finfo.min gives in fp32.  No atomics: a second call is bit-identical.
-#include "common.hpp"
+#include "attn_tile.hpp"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-constexpr int KT = 64;  // keys per tile
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float NEG_BIG = -1.0e30f;
 constexpr int MAX_B = 64;  // samples per launch (the remap / token sets travel by value)
 
 struct MutualArgs {
@@ -38,27 +35,12 @@ struct MutualArgs {
     int src[MAX_B];
 };
 
-__device__ __forceinline__ int vt_pos(int key) {  // key = 16 f + 4 g + r  ->  16 g + 4 f + r
-    return ((key >> 2) & 3) * 16 + (key >> 4) * 4 + (key & 3);
-}
-
 template <int D, int QF, bool DBUF, bool HAS_CLS>
 __global__ __launch_bounds__(256, (D <= 96 ? 2 : 1)) void attn_mutual_kernel(const MutualArgs p) {
-    constexpr int NW = 4, NT = 256;
-    constexpr int NC = D / 32;
-    constexpr bool TAIL16 = (D % 32) != 0;
-    static_assert(D % 32 == 0 || D % 32 == 8 || D % 32 == 16, "head_dim % 32 must be 0, 8 or 16");
-    constexpr int DQK = NC * 32 + (TAIL16 ? 16 : 0);
-    constexpr int DV = (D + 15) / 16 * 16;
-    constexpr bool ONES = DV > D;  // a padding row of V^T holds 1.0: the PV MFMA also yields the softmax denominator
-    constexpr int NDF = DV / 16;
-    constexpr int DCH = D / 8;
-    constexpr int KROW = DQK + 8;
-    constexpr int VROW = KT + 8;
-    constexpr int KCH = (KT * DCH + NT - 1) / NT;
-    constexpr int VCH = ((KT / 2) * DCH + NT - 1) / NT;
-    constexpr int NBUF = DBUF ? 2 : 1;
-    constexpr int KSZ = KT * KROW, VSZ = DV * VROW;
+    using T = AttnTile<D, QF, 4, DBUF>;
+    constexpr bool TAIL16 = T::TAIL16, ONES = T::ONES;
+    constexpr int NW = 4, NT = T::NT, NC = T::NC, DQK = T::DQK, DV = T::DV, NDF = T::NDF, DCH = T::DCH, KROW = T::KROW, VROW = T::VROW, KCH = T::KCH, VCH = T::VCH,
+                  NBUF = T::NBUF, KSZ = T::KSZ, VSZ = T::VSZ;
 
     __shared__ __attribute__((aligned(16))) bf16_t smem[NBUF * (KSZ + VSZ)];
     __shared__ __attribute__((aligned(16))) uint8_t sKc[NBUF * KT];
@@ -67,7 +49,7 @@ __global__ __launch_bounds__(256, (D <= 96 ? 2 : 1)) void attn_mutual_kernel(con
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, lg = lane >> 4;
-    constexpr int QB = NW * 16 * QF;
+    constexpr int QB = T::QB;
     const int N = p.N;
     const int nqb = (N + QB - 1) / QB;
     const int vb = xcd_remap(blockIdx.x, nqb * p.B * p.H);
@@ -191,16 +173,7 @@ __global__ __launch_bounds__(256, (D <= 96 ? 2 : 1)) void attn_mutual_kernel(con
 #pragma unroll
         for (int i = 0; i < VCH; ++i) {
             if ((KT / 2) * DCH % NT == 0 || tid + i * NT < (KT / 2) * DCH) {
-                const int pos = vt_pos(2 * v_pr[i]);
-                const uint32_t a0[4] = {rv[i][0].x, rv[i][0].y, rv[i][0].z, rv[i][0].w};
-                const uint32_t a1[4] = {rv[i][1].x, rv[i][1].y, rv[i][1].z, rv[i][1].w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const uint32_t lo = __builtin_amdgcn_perm(a1[e], a0[e], 0x05040100u);
-                    const uint32_t hi = __builtin_amdgcn_perm(a1[e], a0[e], 0x07060302u);
-                    *reinterpret_cast<uint32_t*>(dV + (v_c[i] * 8 + 2 * e) * VROW + pos) = lo;
-                    *reinterpret_cast<uint32_t*>(dV + (v_c[i] * 8 + 2 * e + 1) * VROW + pos) = hi;
-                }
+                store_vt_pair(dV, VROW, v_c[i], vt_pos(2 * v_pr[i]), rv[i][0], rv[i][1]);
             }
         }
         if (HAS_CLS) {
@@ -366,7 +339,7 @@ __global__ __launch_bounds__(256, (D <= 96 ? 2 : 1)) void attn_mutual_kernel(con
 
 template <int D, int QF, bool DBUF>
 int launch_mutual(const MutualArgs& a, hipStream_t stream) {
-    constexpr int QB = 4 * 16 * QF;
+    constexpr int QB = AttnTile<D, QF, 4, DBUF>::QB;
     const long blocks = (long)((a.N + QB - 1) / QB) * a.B * a.H;
     dim3 grid((unsigned)blocks), block(256);
     if (a.qcls) hipLaunchKernelGGL((attn_mutual_kernel<D, QF, DBUF, true>), grid, block, 0, stream, a);

@@ -191,6 +191,51 @@ def test_mutual_empty_class_is_the_mean_of_v(ops, RC, D, S):
     assert float((r[1][:, fg] - V[0].mean(1)[:, None, :]).abs().max()) < 1e-12
 
 
+@pytest.mark.parametrize("N", (1, 65, 300))
+def test_mutual_identity_equals_general_attention_bitwise(ops, N):
+    """attn_mutual_kernel is the twin of attention.hip's attn_kernel (same tile constants, csrc/attn_tile.hpp; its own copy of the body): with the
+    identity remap and no classes the mutual launch and ops.attention (head dim 64 reaches attn_kernel<64, 2, 4, true, 0, false> with no knob set) run the same arithmetic in the
+    same order on the same packed operands, so their outputs are equal bit for bit (N: one row, a one-key tail tile, a ragged last query block)."""
+    B, H, D = 2, 2, 64
+    buf, st, _ = _packed_operands(B, H, N, D, 64 + N)
+    inner = H * D
+    dev = buf.to(DEV)
+    got = ops.attention_mutual(dev, dev[:, inner:], dev[:, 2 * inner:], B, H, N, D, D ** -0.5, st, st, st, tuple(range(B)))
+    want = ops.attention(dev, dev[:, inner:], dev[:, 2 * inner:], B, H, N, N, D, D ** -0.5, st, st, st)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(want.float()).all())
+    diff = int((got.view(torch.int16) != want.view(torch.int16)).sum())
+    print(f"mutual (identity, no classes) vs general attention, D={D} N={N}: {diff} differing elements of {got.numel()}")
+    assert torch.equal(got, want)
+
+
+_TWIN_CHILD = """
+import sys, torch
+sys.path.insert(0, {tests!r}); sys.path.insert(0, {root!r})
+import test_hip_masactrl as TM
+from anyedit_amd import ops
+for N in (1, 65, 300):
+    buf, st, _ = TM._packed_operands(2, 2, N, 40, 40 + N)
+    dev = buf.to("cuda")
+    got = ops.attention_mutual(dev, dev[:, 80:], dev[:, 160:], 2, 2, N, 40, 40 ** -0.5, st, st, st, (0, 1))
+    want = ops.attention(dev, dev[:, 80:], dev[:, 160:], 2, 2, N, N, 40, 40 ** -0.5, st, st, st)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(want.float()).all()), N
+    assert torch.equal(got, want), "N=%d: %d differing elements" % (N, int((got.view(torch.int16) != want.view(torch.int16)).sum()))
+print("twins equal")
+"""
+
+
+def test_mutual_identity_equals_general_attention_bitwise_at_head_dim_40():
+    """The same equality at head dim 40, which has the K = 16 tail operand and the ones row.  Head dim 40 reaches attn_kernel<40, 2, 4, true, 0, false> only
+    with AE_ATTN_FAST=0, which attention.hip reads once per process: one child process under it runs N in {1, 65, 300}."""
+    import subprocess
+    env = dict(os.environ, AE_ATTN_FAST="0")
+    r = subprocess.run([sys.executable, "-c", _TWIN_CHILD.format(tests=HERE, root=ROOT)], capture_output=True, text=True, timeout=120, env=env)
+    print(r.stdout, r.stderr[-2000:])
+    assert r.returncode == 0 and "twins equal" in r.stdout
+
+
 def test_mutual_refuses_other_head_dims(ops):
     from anyedit_amd._lib import lib, AnyEditHipError, check
     import ctypes
