@@ -225,21 +225,32 @@ class Tape:
         return wr
 
     # ------------------------------------------------------------------ operators
+    def _refuse_vector_grads(self, op, bias, bname, addvec):
+        """The GEMM / conv nodes produce a bias gradient only for a bias registered as trainable (`ae_colsum_bf16_f32`) and none for
+        `addvec`: a gradient asked for either of them any other way would be dropped without a word."""
+        if self.needs(addvec):
+            raise RuntimeError(f"autodiff: {op} addvec is not differentiable here (add it with an op of its own)")
+        if bname is None and self.needs(bias):
+            raise RuntimeError(f"autodiff: {op} bias is differentiable only as a trainable leaf of a gemm (mark_trainable)")
+
     def gemm(self, a, w, bias=None, residual=None, addvec=None, rows_per_batch=0, epilogue=ops.EPI_NONE, out_f32=False, a2=None,
              out=None):
+        wname = self.trainable.get(id(w))
+        bname = self.trainable.get(id(bias)) if bias is not None else None
+        differentiated = bool(self.needs(a) or self.needs(a2) or self.needs(residual) or wname or bname)
+        # what the node cannot differentiate is refused before the forward is launched
+        self._refuse_vector_grads("gemm", bias, bname, addvec)
+        if differentiated and (epilogue != ops.EPI_NONE or out_f32):
+            raise RuntimeError("autodiff: fused activations / fp32 outputs are not differentiable here (use the un-fused ops)")
         with self.paused():
             y = ops.gemm(a, w, bias=bias, residual=residual, addvec=addvec, rows_per_batch=rows_per_batch, epilogue=epilogue,
                          out_f32=out_f32, a2=a2, out=out)
-        wname = self.trainable.get(id(w))
-        bname = self.trainable.get(id(bias)) if bias is not None else None
         ins = [a, a2, residual]
         if wname is not None or bname is not None:
             self.require(y)
             self.keep.extend([y, a])
-        if not (self.needs(a) or self.needs(a2) or self.needs(residual) or wname or bname):
+        if not differentiated:
             return y
-        if epilogue != ops.EPI_NONE or out_f32:
-            raise RuntimeError("autodiff: fused activations / fp32 outputs are not differentiable here (use the un-fused ops)")
         K1 = a.shape[1]
 
         def bwd():
@@ -275,6 +286,9 @@ class Tape:
         return y
 
     def conv3x3(self, x, w, bias, B, H, W, addvec=None, residual=None, stride=1, upsample2x=False, out_f32=False, out=None):
+        self._refuse_vector_grads("conv3x3", bias, None, addvec)
+        if bias is not None and id(bias) in self.trainable:
+            raise RuntimeError("autodiff: conv3x3 has no bias gradient here (the convolutions of the training step are frozen)")
         with self.paused():
             y, Ho, Wo = ops.conv3x3(x, w, bias, B, H, W, addvec=addvec, residual=residual, stride=stride, upsample2x=upsample2x,
                                     out_f32=out_f32, out=out)
@@ -300,6 +314,8 @@ class Tape:
                 raise RuntimeError("autodiff: rotated conv weight does not match the gradient's channel count")
             if stride == 2:      # adjoint of the stride-2 conv: zero-insert upsampling folded into the gather
                 dx, _, _ = ops.conv3x3(dy.contiguous(), wr, None, B, Ho, Wo, upsample2x=2)
+                if (2 * Ho, 2 * Wo) != (H, W):   # odd map: row 2Ho-1 / column 2Wo-1 of the adjoint lies in the forward's zero padding — dropping it is exact
+                    dx = dx.view(B, 2 * Ho, 2 * Wo, cin)[:, :H, :W].reshape(B * H * W, cin)
             elif upsample2x:     # forward was conv(nearest_x2(x)): adjoint conv at 2H x 2W, then 2x2 block sums
                 dxv, _, _ = ops.conv3x3(dy.contiguous(), wr, None, B, Ho, Wo)
                 dx = ops.sumpool2x2(dxv, B, H, W)
