@@ -164,6 +164,8 @@ SIGNATURES = {
     "ae_attn_mutual_bf16": [c_void_p] * 4 + [c_int] * 4 + [c_long] * 12 + [c_float, ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p],
     "ae_attn_token_map_bf16": [c_void_p] * 3 + [c_int] * 5 + [c_long] * 6 + [c_float, ctypes.POINTER(ctypes.c_ulonglong), c_int, c_void_p],
     "ae_masactrl_classes": [c_void_p, c_long, c_int, c_int, c_float, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p],
+    "ae_attn_p2p_bf16": [c_void_p] * 4 + [c_int] * 5 + [c_long] * 12 + [c_float, ctypes.POINTER(c_int)] + [c_void_p] * 4 + [ctypes.POINTER(c_int), c_int, c_int, c_void_p],
+    "ae_p2p_local_blend_f32": [ctypes.POINTER(c_void_p), c_int, c_int, c_int, ctypes.POINTER(ctypes.c_ulonglong), c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
 }
 _RESTYPES = {"ae_last_error": ctypes.c_char_p, "ae_groupnorm_workspace_floats": c_long, "ae_conv3x3_workspace_floats": c_long,
              "ae_groupnorm_bwd_workspace_floats": c_long, "ae_attn_fp8_workspace_bytes": c_long, "ae_attn_bwd_workspace_floats": c_long,

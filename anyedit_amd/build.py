@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libanyedit_hip.so")
 SOURCES = ["c_api.hip", "gemm_conv.hip", "gemm_rowpanel.hip", "ff_fused.hip", "attention.hip", "attention_fast.hip", "attention_fp8.hip", "attention_bwd.hip", "norm.hip", "elementwise.hip", "backward.hip", "gate.hip", "expert_kv.hip", "msda.hip",
-           "sam_decoder.hip", "clip_text.hip", "clip_vision.hip", "dino_vision.hip", "swin.hip", "gdino_encoder.hip", "gdino_decoder.hip", "gdino_text.hip", "gdino_neck.hip", "hed.hip", "dpt.hip", "uniformer.hip", "upernet.hip", "masactrl.hip"]
+           "sam_decoder.hip", "clip_text.hip", "clip_vision.hip", "dino_vision.hip", "swin.hip", "gdino_encoder.hip", "gdino_decoder.hip", "gdino_text.hip", "gdino_neck.hip", "hed.hip", "dpt.hip", "uniformer.hip", "upernet.hip", "masactrl.hip", "prompt2prompt.hip"]
 # Per-file flags.
 #  * -ffinite-math-only (attention kernels): no NaN / Inf semantics are relied on (masked logits are a finite -1e30) -> fmaxf compiles to
 #    bare v_max / v_max3.

@@ -2009,6 +2009,117 @@ def masactrl_classes(maps, S, R, thres, pairs, cls, counts):
     return cls, counts
 
 
+# --------------------------------------------------------------------------- Prompt-to-Prompt attention control (csrc/prompt2prompt.hip)
+P2P_HEAD_DIMS = (40, 64, 80, 160)
+P2P_MAX_BATCH = 64
+P2P_MAX_KEYS = 128
+P2P_BLEND_MAX_LAYERS, P2P_BLEND_MAX_SIDE = 8, 32
+
+
+def attention_p2p(q, k, v, B, H, N, Nk, D, scale, q_strides, k_strides, v_strides, base, M=None, c=None, d=None, store=None, store_row=None,
+                  accumulate=False, out=None, o_strides=None, want_out=True):
+    """Short-key cross-attention in which an edited sample's probabilities come from its base sample's (ae_attn_p2p_bf16).  q / k / v: bf16 tensors
+    addressed via (batch, head, row) element strides, as `attention` takes them.  base: B host ints; base[b] == b: unedited, P' = softmax(q_b k_b^T);
+    otherwise P' = (P_base M[b]) * c[b] + P_own * d[b], not renormalised.  M fp32 [B, Nk, Nk] contiguous or None (= the identity for every sample);
+    c, d fp32 [B, Nk] contiguous (needed when any sample is edited).  store fp32 [rows, N, Nk] contiguous with store_row (B host ints, -1 = not
+    stored): store[store_row[b]] (+)= sum over heads of P'[b] (accumulate: add).  want_out=False: no PV product, only the store is written (v may be
+    None) and None is returned; otherwise out: [B, N, H*D] bf16."""
+    _chk(q, BF16, "attention_p2p.q")
+    _chk(k, BF16, "attention_p2p.k")
+    if D not in P2P_HEAD_DIMS or not 1 <= Nk <= P2P_MAX_KEYS or not 1 <= B <= P2P_MAX_BATCH or N < 1 or H < 1:
+        raise ValueError(f"attention_p2p: head dims {P2P_HEAD_DIMS}, Nk <= {P2P_MAX_KEYS} and B <= {P2P_MAX_BATCH} are covered, got B={B} H={H} N={N} "
+                         f"Nk={Nk} D={D}")
+    base = tuple(int(s) for s in base)
+    if len(base) != B or any(s < 0 or s >= B for s in base):
+        raise ValueError(f"attention_p2p: base needs {B} sample indices in [0, {B}), got {base}")
+    if any(base[s] != s for s in base):
+        raise ValueError(f"attention_p2p: a base sample must be unedited (base[base[b]] == base[b]), got {base}")
+    edited = any(s != b for b, s in enumerate(base))
+    if M is not None:
+        _chk(M, torch.float32, "attention_p2p.M", 3)
+        if tuple(M.shape) != (B, Nk, Nk) or not M.is_contiguous():
+            raise ValueError(f"attention_p2p.M: expected a contiguous fp32 [{B}, {Nk}, {Nk}] tensor, got {tuple(M.shape)}")
+    if edited and (c is None or d is None):
+        raise ValueError("attention_p2p: an edited sample needs c and d")
+    for t, n in ((c, "c"), (d, "d")):
+        if t is not None:
+            _chk(t, torch.float32, "attention_p2p." + n, 2)
+            if tuple(t.shape) != (B, Nk) or not t.is_contiguous():
+                raise ValueError(f"attention_p2p.{n}: expected a contiguous fp32 [{B}, {Nk}] tensor, got {tuple(t.shape)}")
+    rows, rarr = 0, None
+    if store is not None:
+        _chk(store, torch.float32, "attention_p2p.store", 3)
+        rows = store.shape[0]
+        if tuple(store.shape[1:]) != (N, Nk) or not store.is_contiguous():
+            raise ValueError(f"attention_p2p.store: expected a contiguous fp32 [rows, {N}, {Nk}] tensor, got {tuple(store.shape)}")
+        if store_row is None:
+            raise ValueError("attention_p2p: a store needs store_row")
+        store_row = tuple(int(r) for r in store_row)
+        kept = [r for r in store_row if r >= 0]
+        if len(store_row) != B or any(r < -1 or r >= rows for r in store_row) or len(set(kept)) != len(kept):
+            raise ValueError(f"attention_p2p: store_row needs {B} distinct rows in [0, {rows}) or -1, got {store_row}")
+        rarr = (ctypes.c_int * B)(*store_row)
+    elif store_row is not None or accumulate:
+        raise ValueError("attention_p2p: store_row / accumulate without a store")
+    if want_out:
+        _chk(v, BF16, "attention_p2p.v")
+        if out is None:
+            out = torch.empty(B, N, H * D, dtype=BF16, device=q.device)
+        else:
+            _chk(out, BF16, "attention_p2p.out")
+        if o_strides is None:
+            o_strides = (N * H * D, D, H * D)
+    else:
+        if store is None:
+            raise ValueError("attention_p2p: want_out=False needs a store to write")
+        out, o_strides = None, (0, 0, 0)
+        if v is None:
+            v_strides = (0, 0, 0)
+    barr = (ctypes.c_int * B)(*base)
+    check(lib.ae_attn_p2p_bf16(_p(q), _p(k), _p(v), _p(out), B, H, N, Nk, D, *q_strides, *k_strides, *v_strides, *o_strides, float(scale), barr, _p(M),
+                               _p(c), _p(d), _p(store), rarr, rows, 1 if accumulate else 0, _s()), "ae_attn_p2p_bf16")
+    return out
+
+
+def p2p_local_blend(maps, S, Nk, token_sets, threshold, x, out=None):
+    """LocalBlend.__call__ in one launch with no read-back (ae_p2p_local_blend_f32).  maps: 1 .. 8 fp32 [2, S*S, Nk] contiguous store maps (head
+    sums; any positive common factor is removed by the normalisation); token_sets: two iterables of token indices below Nk; x fp32 [2, C, h, w]
+    contiguous.  mask_b = (resize(maxpool3x3(sum_layers sum_{j in set_b} map[b, :, j])) / its maximum) > threshold; out[1] = x[1] where mask_0 or
+    mask_1, else x[0]; out[0] = x[0].  out: None (allocated), x itself (in place) or another fp32 [2, C, h, w] buffer."""
+    maps = list(maps)
+    if not 1 <= len(maps) <= P2P_BLEND_MAX_LAYERS or not 1 <= S <= P2P_BLEND_MAX_SIDE or not 1 <= Nk <= P2P_MAX_KEYS:
+        raise ValueError(f"p2p_local_blend: 1 .. {P2P_BLEND_MAX_LAYERS} maps of side <= {P2P_BLEND_MAX_SIDE} with Nk <= {P2P_MAX_KEYS} are covered, "
+                         f"got {len(maps)} maps, S={S}, Nk={Nk}")
+    for i, m in enumerate(maps):
+        _chk(m, torch.float32, f"p2p_local_blend.maps[{i}]", 3)
+        if m.shape[0] != 2:
+            raise ValueError(f"p2p_local_blend: exactly two samples (the reference's mask[:1] + mask[1:] broadcast holds for two prompts only), got "
+                             f"maps[{i}] of shape {tuple(m.shape)}")
+        if tuple(m.shape) != (2, S * S, Nk) or not m.is_contiguous():
+            raise ValueError(f"p2p_local_blend.maps[{i}]: expected a contiguous fp32 [2, {S * S}, {Nk}] tensor, got {tuple(m.shape)}")
+    _chk(x, torch.float32, "p2p_local_blend.x", 4)
+    if x.shape[0] != 2:
+        raise ValueError(f"p2p_local_blend: exactly two samples (the reference's mask[:1] + mask[1:] broadcast holds for two prompts only), got x of "
+                         f"shape {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError("p2p_local_blend.x: expected a contiguous tensor")
+    token_sets = [tuple(int(t) for t in s) for s in token_sets]
+    if len(token_sets) != 2 or any(t >= Nk for s in token_sets for t in s):
+        raise ValueError(f"p2p_local_blend: need 2 token sets with indices below Nk={Nk}, got {token_sets}")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _chk(out, torch.float32, "p2p_local_blend.out", 4)
+        if tuple(out.shape) != tuple(x.shape) or not out.is_contiguous():
+            raise ValueError(f"p2p_local_blend.out: expected a contiguous fp32 {tuple(x.shape)} tensor, got {tuple(out.shape)}")
+    words = [w for s in token_sets for w in token_set_words(s)]
+    warr = (ctypes.c_ulonglong * 4)(*words)
+    parr = (ctypes.c_void_p * len(maps))(*(m.data_ptr() for m in maps))
+    _, C, h, w = x.shape
+    check(lib.ae_p2p_local_blend_f32(parr, len(maps), S, Nk, warr, float(threshold), _p(x), _p(out), C, h, w, _s()), "ae_p2p_local_blend_f32")
+    return out
+
+
 def rows_to_nchw_out(x, out):
     """channels-last bf16 rows [B*H*W, C] contiguous -> the given [B, C, H, W] buffer (fp32 or bf16, contiguous): `rows_to_nchw` into a
     buffer the caller owns (no allocation)."""

@@ -758,6 +758,38 @@ int ae_attn_token_map_bf16(const void* q, const void* k, float* out, int B, int 
 int ae_masactrl_classes(const float* maps, long map_ld, int S, int R, float thres, int npairs, const int* sample, const int* out_row, unsigned char* cls,
                         int* counts, void* stream);
 
+/* ---- Prompt-to-Prompt attention control (csrc/prompt2prompt.hip; AnyEdit_Collection/other_modules/prompt2prompt/prompt_to_prompt_stable.py, registered on
+ * the UNet by ptp_utils.py:175-273).  The reference hook materialises attention_probs ([B h, N, 77]) of every attention call and edits it in torch; these
+ * entry points form no logit or probability buffer.  No atomics, fixed summation orders (a second call is bit-identical), current stream only, no host
+ * synchronisation, no allocation.
+ * ae_attn_p2p_bf16: prompt_to_prompt_stable.py:183-199 (AttentionControlEdit.forward: attn[1:] = replace_cross_attention(base, own) alpha + (1 - alpha)
+ *   own), :216-217 (AttentionReplace: einsum with the mapper), :228-231 (AttentionRefine: gather and alphas), :243-248 (AttentionReweight: the equalizer,
+ *   optionally over a previous controller), :132-136 and :138-146 (AttentionStore: the kept maps and their sums over the steps), followed by the
+ *   hook's bmm with V (ptp_utils.py:226).  For a sample b with s = base[b] != b, per head:
+ *     P_base = softmax_j(scale q_s k_s^T), P_own = softmax_j(scale q_b k_b^T), P' = (P_base M_b) * c_b + P_own * d_b, out_b = P' v_b;
+ *   for base[b] == b, P' = P_own.  P' is not renormalised and may be negative.  store[store_row[b]][i][j] (+)= sum_h P'[b,h,i,j] (the head SUM, heads
+ *   added in index order; accumulate != 0 adds to the store, 0 overwrites it).  (M, c, d) per controller, a = cross_replace_alpha[cur_step, e]:
+ *   Replace (mapper_e, a, 1 - a); Refine (one-hot gather of mapper_e, alphas_e a, 1 - alphas_e a); Reweight (identity, eq_e a, 1 - a); Reweight over a
+ *   previous (M0, c0, d0): (M0, c0 eq a, d0 eq a + 1 - a).
+ *   q / k / v bf16 read in place through (batch, head, row) element strides as ae_attn_fwd_bf16 takes them (rows 16-byte aligned); out bf16 through
+ *   o-strides (multiples of 4), or NULL: no PV product, only the store is written (v may then be NULL).  base, store_row: B host ints read during the
+ *   call; base[b] in [0, B) and base[base[b]] == base[b] (a base that is itself edited is refused); store_row[b] in [-1, store_rows), -1 = not stored,
+ *   no two samples share a row.  M fp32 [B, Nk, Nk] or NULL: NULL is the identity for every sample (no dense identity is read); c, d fp32 [B, Nk]
+ *   (rows of unedited samples are not read); store fp32 [store_rows, N, Nk] or NULL.  fp32 logits, softmax, P_base M, blend and P' V on the VALU (no
+ *   bf16 rounding between the operands and the one rounding of the output); a key past Nk has probability exactly 0; query rows past N are clamped for
+ *   loads and never stored.  B <= 64, Nk <= 128, head_dim 40 / 64 / 80 / 160, any H, N >= 1; anything else: AE_ERR_UNSUPPORTED with a message.
+ * ae_p2p_local_blend_f32: prompt_to_prompt_stable.py:61-73 (LocalBlend.__call__) in one launch with no read-back.  maps: host array of `nlayers`
+ *   (1 .. 8) device pointers, each an fp32 [2, S S, Nk] store map (S <= 32); token_sets: 4 host uint64, bit j % 64 of word 2 b + j / 64 set iff token j
+ *   is in sample b's set.  m_b[p] = sum_layers sum_{j in set_b} map_l[b][p][j] (the reference's mean over heads and layers is a positive factor its
+ *   normalisation removes) -> 3x3 max-pool, stride 1, pad 1 -> nearest resize S -> (h, w), src = min(floor(dst S / out), S - 1) -> divided by the
+ *   sample's maximum (fp32 IEEE) -> > threshold -> mask = mask_0 OR mask_1 -> out[1] = mask ? x[1] : x[0], out[0] = x[0].  x, out fp32 [2, C, h, w]
+ *   contiguous, out == x allowed.  A map whose maximum is 0 is 0 / 0 = NaN in the reference, which compares false: its mask is 0 here.              */
+int ae_attn_p2p_bf16(const void* q, const void* k, const void* v, void* out, int B, int H, int N, int Nk, int D, long q_sb, long q_sh, long q_sn, long k_sb,
+                     long k_sh, long k_sn, long v_sb, long v_sh, long v_sn, long o_sb, long o_sh, long o_sn, float scale, const int* base, const float* M,
+                     const float* c, const float* d, float* store, const int* store_row, int store_rows, int accumulate, void* stream);
+int ae_p2p_local_blend_f32(const float* const* maps, int nlayers, int S, int Nk, const unsigned long long* token_sets, float threshold, const float* x,
+                           float* out, int C, int h, int w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
